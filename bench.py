@@ -13,11 +13,14 @@ bs=32/GPU batch at 640x480, fp32: forward, backward driven by fixed output cotan
 optimizer.py:29-36.  Inputs are resident in HBM before the timed region.  Weights: deterministic
 random init; data: the reference's own synthetic generator (inference_time_whole_model.py:519-545).
 
-Rank 0 prints ONE JSON line.  `roofline` is measured live with HIP events around every 4th launch
-(per kernel class) of the MFMA convolution kernels inside the timed steps (emsa_prof_* C-ABI;
-bracketing every launch costs 3 % of the step, every 4th < 1 %); `cpu_baseline` times the
-oracle (plain PyTorch CPU restatement, tests infrastructure) on the host cores for a bounded
-sample of the same workload.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times --steps steps and reports
+`value` / `ms_per_step`; everything else is measured only with --full: `roofline` is measured live
+with HIP events around every 4th launch (per kernel class) of the MFMA convolution kernels inside
+the timed steps (emsa_prof_* C-ABI; bracketing every launch costs 3 % of the step, every 4th < 1 %)
+and in single-stream steps behind them, `whole_step` counts the bytes of one more step, and
+`cpu_baseline` times the oracle (plain PyTorch CPU restatement, tests infrastructure) on the host
+cores for a bounded sample of the same workload.  --dump-outputs DIR writes what the last timed
+step returned (dump_outputs).
 """
 import argparse
 import ctypes
@@ -44,6 +47,15 @@ def parse():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline value does not need: the per-kernel HIP-event '
+                         'timing and `roofline` / `roofline_by_class` / `conv_kernels` (with their '
+                         'single-stream steps behind the timed region), `whole_step` and `cpu_baseline`')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed as DIR/<name>.npy '
+                         '(float32; a fixed, seeded sample of large arrays, 64 MB at most).  The same '
+                         'arguments give the same inputs and outputs: the forward outputs bit for bit, '
+                         'the gradients to the fp32-atomics jitter of a few weight gradients (~1e-7)')
     ap.add_argument('--batch-size', type=int, default=32, help='per GPU')
     ap.add_argument('--height', type=int, default=480)
     ap.add_argument('--width', type=int, default=640)
@@ -176,6 +188,55 @@ def flatten_outputs(outs):
         for s in sides:
             flat += list(s) if isinstance(s, tuple) else [s]
     return flat
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _sample(t, idx):
+    """elements of `t` at the flat indices `idx` of its logical (NCHW) order, without a contiguous
+    copy of `t` (the activations are NHWC in memory)"""
+    coords = np.unravel_index(idx, tuple(t.shape))
+    return t[tuple(torch.from_numpy(c).to(t.device) for c in coords)]
+
+
+def dump_outputs(dirname, result, params):
+    """--dump-outputs: what the last timed step handed its caller -- every flattened model output
+    (`output_NN`), the loss of a --losses step (`loss`) and, for a training step, the parameters after
+    the update and their gradients (`param_sample`, `grad_sample`: the same elements of the
+    concatenation of all parameters in model order) -- as float32 .npy files.  An array larger than
+    its share of the 64 MB is stored as a fixed, seeded sample of its elements (sorted flat indices of
+    the logical layout), so that two builds run with the same arguments write comparable files."""
+    loss, out = result
+    os.makedirs(dirname, exist_ok=True)
+    flat = flatten_outputs(out)
+    arrays = {}
+    cap = min(1 << 19, (DUMP_MAX_BYTES // 2) // (4 * max(1, len(flat))))   # elements per output
+    for i, t in enumerate(flat):
+        t = t.detach()
+        if t.numel() > cap:
+            t = _sample(t, np.sort(np.random.default_rng(1000 + i).integers(0, t.numel(), cap)))
+        arrays[f'output_{i:02d}'] = t.float().cpu().numpy()
+    if loss is not None:
+        arrays['loss'] = loss.detach().float().cpu().numpy()
+    if params:
+        sizes = np.array([p.numel() for p in params], dtype=np.int64)
+        start = np.concatenate([[0], np.cumsum(sizes)])
+        k = min(1 << 20, int(start[-1]))
+        idx = np.sort(np.random.default_rng(7).integers(0, start[-1], k))
+        owner = np.searchsorted(start, idx, side='right') - 1
+        vals, grads = [], []
+        for j in np.unique(owner):
+            p, local = params[j], idx[owner == j] - start[j]
+            vals.append(_sample(p.detach(), local).float().cpu())
+            grads.append(torch.zeros(len(local)) if p.grad is None
+                         else _sample(p.grad.detach(), local).float().cpu())
+        arrays['param_sample'] = torch.cat(vals).numpy()
+        arrays['grad_sample'] = torch.cat(grads).numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f'--dump-outputs: {total} bytes'
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + '.npy'), a)
 
 
 def cpu_replica_worker(args):
@@ -588,14 +649,18 @@ def run(args):
     else:
         buckets = GradientBuckets(params, force_collectives=args.force_dist,
                                   average=args.torch_optimizer, comm_dtype=comm_dtype)
-    # LR rule of the reference: 0.01 * batch/8 (args.py:1338-1344); tiny here so that the random
-    # net stays finite over the benchmark steps
+    # learning rate 0: the update kernels run in full (same reads, writes and arithmetic) but every
+    # step starts from the same weights.  With any lr > 0 this random net, driven by fixed output
+    # cotangents, amplifies the fp32-atomics jitter of a few weight gradients (1e-7 after one step)
+    # from step to step -- 2e-5 in the outputs of step 2, O(1) by step 4 at 640x480 -- and two runs
+    # with the same arguments would no longer compute the same last step (--dump-outputs)
+    lr = 0.0
     if args.torch_optimizer:
-        opt = torch.optim.SGD(params, lr=1e-5, momentum=0.9, weight_decay=1e-4, nesterov=True)
+        opt = torch.optim.SGD(params, lr=lr, momentum=0.9, weight_decay=1e-4, nesterov=True)
     else:
         # one fused kernel per flat bucket (emsa_sgd_nesterov), same update rule
         from emsanet_amd.optim import FusedSGD
-        opt = FusedSGD(buckets, lr=1e-5, momentum=0.9, weight_decay=1e-4)
+        opt = FusedSGD(buckets, lr=lr, momentum=0.9, weight_decay=1e-4)
     cots = None
     crit, targets = None, None
     if args.losses and not args.eval:
@@ -610,28 +675,28 @@ def run(args):
 
     def step(fresh=None):
         # `fresh`: a batch that was just staged from host memory (--h2d); default: the HBM-resident one
+        # returns (loss or None, model outputs): what the step hands its caller (--dump-outputs)
         nonlocal cots
         b = batch if fresh is None else fresh
         if args.eval:
             if graphed is not None:
-                graphed(b)
-                return
+                return None, graphed(b)
             with torch.no_grad():
-                model(b)
-            return
+                return None, model(b)
         if train_graph is not None:
-            train_graph.replay(fresh)
-            return
+            return train_graph.replay(fresh)
         buckets.reset()
         if crit is not None:
             # --losses: the complete training step (all task losses on device, weighted like the
             # reference's training command) instead of fixed output cotangents
-            total, _ = crit(model(b), targets)
+            out = model(b)
+            total, _ = crit(out, targets)
             total.backward()
             buckets.finish()
             opt.step()
-            return
-        flat = flatten_outputs(model(b))
+            return total, out
+        out = model(b)
+        flat = flatten_outputs(out)
         if cots is None:
             g = torch.Generator(device='cpu').manual_seed(4321)
             cots = [(torch.randn(t.shape, generator=g) * 1e-3).to(dev).contiguous(
@@ -640,6 +705,7 @@ def run(args):
         torch.autograd.backward(flat, cots)
         buckets.finish()
         opt.step()
+        return None, out
 
     def barrier():
         torch.cuda.synchronize()
@@ -689,7 +755,7 @@ def run(args):
     for _ in range(args.warmup):
         step()
     buckets.reset_stats()
-    timing = not args.no_kernel_timing
+    timing = args.full and not args.no_kernel_timing
     L.emsa_prof_reset()
     # two streams: the roofline comes from the single-stream pass behind the timed region; inside
     # it the launches are only sampled sparsely (every 17th: coprime to the 4 launches of a block)
@@ -704,12 +770,17 @@ def run(args):
     Fn.PROF_REAL_FLOPS = timing      # padded / merged convs report their real FLOPs (stem 7x7x3 ...)
     barrier()
     t0 = time.perf_counter()
+    last = None
     for _ in range(args.steps):
-        step()
+        last = None            # (the outputs of an eager step are not kept through the next one)
+        last = step()
     barrier()
     dt = time.perf_counter() - t0
     L.emsa_prof_enable(0)
     Fn.PROF_REAL_FLOPS = False
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, [] if args.eval else params)
+    del last
     staged = None
     if args.h2d:
         # the same K steps once more with every batch coming from pinned HOST memory as raw uint8 /
@@ -813,7 +884,7 @@ def run(args):
     # time of the timed region and the 8 TB/s HBM roofline, next to the step's FLOPs against the
     # MFMA peak of the arithmetic
     whole_step = None
-    if world == 1 and not args.h2d:
+    if args.full and world == 1 and not args.h2d:
         cnt = [0]
         Fn.BYTES = cnt
         try:
@@ -846,7 +917,7 @@ def run(args):
     # a graph-replayed training step cannot be bracketed by HIP events per launch: its kernels are
     # timed in `roofline_steps` EAGER steps of the same step object (same kernels, same buffers, the
     # collectives included) behind the timed region, on one stream
-    graph_roof = train_graph is not None and not args.eval and args.roofline_steps > 0
+    graph_roof = args.full and train_graph is not None and not args.eval and args.roofline_steps > 0
 
     def eager_twin():
         if hasattr(train_graph, 'eager_step'):
@@ -895,7 +966,7 @@ def run(args):
     pmc_names = ('r06_pmc_traffic.json', 'r05_pmc_traffic.json') \
         if args.dtype == 'f32' else (f'r06_pmc_traffic_{args.dtype}.json', f'r05_pmc_traffic_{args.dtype}.json')
     pmc_stale = None
-    for name in pmc_names:                                             # newest measurement first
+    for name in pmc_names if kernels else ():                          # newest measurement first
         try:
             pmc = json.load(open(os.path.join(ROOT, 'profiles', name)))
             pmc_file = 'profiles/' + name
@@ -1023,7 +1094,7 @@ def run(args):
         workload = (f'{cfg}: {head}, train mode '
                     '(BN batch stats, Dropout2d), step = fwd + bwd ('
                     + ('all task losses on device' if args.losses else 'fixed output cotangents')
-                    + ') + grad all-reduce + SGD-nesterov update'
+                    + ') + grad all-reduce + SGD-nesterov update at lr 0 (fixed weights)'
                     + (' replayed from a hipGraph' if args.graph else ''))
     if roofline is None and whole_step is not None and (args.eval or args.graph):
         # no per-launch brackets (graph replay) or no dominant MFMA class (inference): the roofline
@@ -1078,7 +1149,7 @@ def run(args):
         'h2d_staged': staged,
         'reference_protocol': ref_protocol,
     }
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         out['cpu_baseline'] = cpu_baseline(args)
     else:
         out['cpu_baseline'] = None

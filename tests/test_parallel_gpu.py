@@ -372,7 +372,7 @@ def test_bench_self_launch_two_ranks_gloo():
     import subprocess
     env = dict(os.environ, EMSA_DIST_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--batch-size', '2',
-                        '--steps', '2', '--warmup', '1', '--roofline-steps', '1', '--no-cpu-baseline'],
+                        '--steps', '2', '--warmup', '1', '--full', '--roofline-steps', '1', '--no-cpu-baseline'],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith('{')]

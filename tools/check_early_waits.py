@@ -5,20 +5,24 @@ behind the load, a control-flow join behind the load).  Cross-compiles the sourc
 ISA; exit code 1 if such a wait exists.   usage: python tools/check_early_waits.py"""
 import os
 import re
+import shutil
 import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'emsanet_amd', 'csrc')
 
 
 def isa(src):
-    out = f'/tmp/_early_{os.path.basename(src)}.s'
+    out = os.path.join(tempfile.mkdtemp(), os.path.basename(src) + '.s')     # (private: no shared path)
     subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17',
                     f'-I{ROOT}/include', f'-I{CSRC}', '-munsafe-fp-atomics', '-S',
                     '--cuda-device-only', '-o', out, src], check=True,
                    stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    return open(out).read()
+    txt = open(out).read()
+    shutil.rmtree(os.path.dirname(out))
+    return txt
 
 
 def main():

@@ -2,19 +2,22 @@
 conv_rs_kernel instantiation (it would drain the next tile's LDS-DMA in every iteration); lists the
 vmcnt waits of every instantiation's tile loop.  usage: python tools/check_rs_waits.py [-v]"""
 import os
+import shutil
 import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def kernels():
     src = os.path.join(ROOT, 'emsanet_amd', 'csrc', 'conv_rs.hip')
-    out = '/tmp/conv_rs_check.s'
+    out = os.path.join(tempfile.mkdtemp(), 'conv_rs_check.s')     # (private: no shared path)
     subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17',
                     '-I' + os.path.join(ROOT, 'include'), '-munsafe-fp-atomics', '-S',
                     '--cuda-device-only', src, '-o', out], check=True, capture_output=True)
     txt = open(out).read().split('\n')
+    shutil.rmtree(os.path.dirname(out))
     starts = [i for i, l in enumerate(txt) if l.startswith('_ZN') and 'conv_rs_kernel' in l and ':' in l]
     for k, i in enumerate(starts):
         end = starts[k + 1] if k + 1 < len(starts) else len(txt)

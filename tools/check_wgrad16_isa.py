@@ -7,20 +7,23 @@ for specific instructions):
                             in the K loop, 16-byte LDS stores
 usage: python tools/check_wgrad16_isa.py [-v]"""
 import os
+import shutil
 import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def kernels():
     src = os.path.join(ROOT, 'emsanet_amd', 'csrc', 'conv_mfma.hip')
-    out = '/tmp/conv_mfma_wgrad16_check.s'
+    out = os.path.join(tempfile.mkdtemp(), 'conv_mfma_wgrad16_check.s')     # (private: no shared path)
     subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17',
                     '-I' + os.path.join(ROOT, 'include'), '-I' + os.path.join(ROOT, 'emsanet_amd', 'csrc'),
                     '-munsafe-fp-atomics', '-S', '--cuda-device-only', src, '-o', out],
                    check=True, capture_output=True)
     txt = open(out).read().split('\n')
+    shutil.rmtree(os.path.dirname(out))
     starts = [i for i, l in enumerate(txt) if l.startswith('_ZN') and l.rstrip().endswith(':')
               or (l.startswith('_ZN') and ': ' in l and '@' in l)]
     for k, i in enumerate(starts):
