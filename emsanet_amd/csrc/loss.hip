@@ -13,16 +13,18 @@ namespace {
 constexpr int kPix = 256;     // pixels per block
 
 template <int C4>
-__device__ __forceinline__ void load_tile(const float* __restrict__ x, int ld, long p0, long pixels,
-                                          float* tile) {
+__device__ __forceinline__ void load_tile(const float* __restrict__ x, int ld, int n_classes,
+                                          long p0, long pixels, float* tile) {
   constexpr int LD = C4 * 4 + 4;     // row stride 4k+4 floats: conflict-free ds_read_b128
+  const int ncp = (n_classes + 3) & ~3;
 #pragma unroll
   for (int j = 0; j < C4; ++j) {
     const int idx = threadIdx.x + kPix * j;
     const int px = idx / C4, c4 = idx % C4;
     float4 v = emsa_zero4();
-    // chunks at or beyond the row's pixel stride belong to the next pixel: never touched
-    if (p0 + px < pixels && c4 * 4 < ld) v = emsa_ld4(x + (p0 + px) * (long)ld + c4 * 4);
+    // chunks beyond the padded class count belong to other channels of a wider tensor, to the
+    // next pixel or, behind the last pixel, to nobody: never touched (ld >= ncp is checked)
+    if (p0 + px < pixels && c4 * 4 < ncp) v = emsa_ld4(x + (p0 + px) * (long)ld + c4 * 4);
     emsa_st4(tile + px * LD + c4 * 4, v);
   }
 }
@@ -31,13 +33,13 @@ template <int C4>
 __global__ __launch_bounds__(kPix) void ce_fwd_kernel(const float* __restrict__ logits, int ld,
                                                       const int64_t* __restrict__ target,
                                                       const float* __restrict__ w, int n_classes,
-                                                      long pixels, float eps, float w_sum,
+                                                      long pixels, float eps,
                                                       float* __restrict__ partial) {
   constexpr int LD = C4 * 4 + 4;
   extern __shared__ __attribute__((aligned(16))) float tile[];
   __shared__ float red[2][kPix / 64];
   const long p0 = (long)blockIdx.x * kPix;
-  load_tile<C4>(logits, ld, p0, pixels, tile);
+  load_tile<C4>(logits, ld, n_classes, p0, pixels, tile);
   __syncthreads();
   const long p = p0 + threadIdx.x;
   float loss = 0.f, wt = 0.f;
@@ -50,26 +52,31 @@ __global__ __launch_bounds__(kPix) void ce_fwd_kernel(const float* __restrict__ 
       for (int j = 0; j < C4; ++j)
         *reinterpret_cast<float4*>(v + 4 * j) = emsa_ld4(tile + threadIdx.x * LD + 4 * j);
       float m = -INFINITY, xt = 0.f;
+      int am = 0;
 #pragma unroll
       for (int c = 0; c < C4 * 4; ++c)
         if (c < n_classes) {
-          m = fmaxf(m, v[c]);
+          if (v[c] > m) { m = v[c]; am = c; }
           xt = c == t ? v[c] : xt;
         }
+      // -log p_c = (m - x_c) + log1p(sum_{c' != argmax} exp(x_c' - m)): differences of logits only, so
+      // a common offset of the pixel's logits costs no bits (lse = log(s) + m rounds to ulp(m), which
+      // is larger than the whole loss of a confident pixel), and the largest term, exp(0) = 1, never
+      // enters the fp32 sum (log(1 + 1e-5) from a rounded 1 + 1e-5 has three digits)
       float s = 0.f;
 #pragma unroll
       for (int c = 0; c < C4 * 4; ++c)
-        if (c < n_classes) s += expf(v[c] - m);
+        if (c < n_classes && c != am) s += expf(v[c] - m);
+      const float ls = log1pf(s);
       wt = w[t];
-      const float lse = logf(s) + m;
-      loss = (1.f - eps) * wt * (lse - xt);
+      loss = (1.f - eps) * wt * ((m - xt) + ls);
       if (eps != 0.f) {
         // label smoothing, torch semantics: + eps/C * sum_c w_c * -log p_c
-        float wx = 0.f;
+        float wl = 0.f;
 #pragma unroll
         for (int c = 0; c < C4 * 4; ++c)
-          if (c < n_classes) wx += w[c] * v[c];
-        loss += eps / (float)n_classes * (lse * w_sum - wx);
+          if (c < n_classes) wl += w[c] * ((m - v[c]) + ls);
+        loss += eps / (float)n_classes * wl;
       }
     }
   }
@@ -121,7 +128,7 @@ __global__ __launch_bounds__(kPix) void ce_bwd_kernel(const float* __restrict__ 
   constexpr int LD = C4 * 4 + 4;
   extern __shared__ __attribute__((aligned(16))) float tile[];
   const long p0 = (long)blockIdx.x * kPix;
-  load_tile<C4>(logits, ld, p0, pixels, tile);
+  load_tile<C4>(logits, ld, n_classes, p0, pixels, tile);
   __syncthreads();
   const long p = p0 + threadIdx.x;
   float* row = tile + threadIdx.x * LD;
@@ -140,18 +147,21 @@ __global__ __launch_bounds__(kPix) void ce_bwd_kernel(const float* __restrict__ 
 #pragma unroll
     for (int c = 0; c < C4 * 4; ++c)
       if (c < n_classes) m = fmaxf(m, v[c]);
-    float s = 0.f;
+    // p_t - 1 = -sum_{c != t} p_c: formed from the other classes' sum, because 1/s - 1 of a
+    // confident pixel (s = 1 + 1e-5) is all rounding error
+    float so = 0.f, et = 0.f;
 #pragma unroll
     for (int c = 0; c < C4 * 4; ++c) {
       v[c] = c < n_classes ? expf(v[c] - m) : 0.f;
-      s += v[c];
+      so += c == t ? 0.f : v[c];
+      et = c == t ? v[c] : et;
     }
-    const float k = g * w[t] * (1.f - eps), inv = 1.f / s;
+    const float k = g * w[t] * (1.f - eps), inv = 1.f / (so + et);
     const float ks = g * eps / (float)n_classes;     // label-smoothing term (0 by default)
 #pragma unroll
     for (int c = 0; c < C4 * 4; ++c) {
       const float pc = v[c] * inv;
-      float d = k * (pc - (c == t ? 1.f : 0.f));
+      float d = k * (c == t ? -so * inv : pc);
       if (eps != 0.f && c < n_classes) d += ks * (w_sum * pc - w[c]);
       v[c] = c < n_classes ? d : 0.f;
     }
@@ -166,18 +176,19 @@ __global__ __launch_bounds__(kPix) void ce_bwd_kernel(const float* __restrict__ 
   for (int j = 0; j < C4; ++j) {
     const int idx = threadIdx.x + kPix * j;
     const int px = idx / C4, c4 = idx % C4;
-    if (p0 + px < pixels && c4 * 4 < ld_d)
+    // the padded class count and no further: dlogits may be a channel slice of a wider tensor
+    if (p0 + px < pixels && c4 * 4 < ((n_classes + 3) & ~3))
       emsa_st4(dlogits + (p0 + px) * (long)ld_d + c4 * 4, emsa_ld4(tile + px * LD + c4 * 4));
   }
 }
 
 template <int C4>
 int launch_fwd(const float* x, int ld, const int64_t* t, const float* w, int nc, long pixels,
-               float eps, float w_sum, float* partial, float* out, hipStream_t st) {
+               float eps, float* partial, float* out, hipStream_t st) {
   const int grid = (int)((pixels + kPix - 1) / kPix);
   const size_t lds = (size_t)kPix * (C4 * 4 + 4) * sizeof(float);
   hipLaunchKernelGGL(ce_fwd_kernel<C4>, dim3(grid), dim3(kPix), lds, st, x, ld, t, w, nc, pixels,
-                     eps, w_sum, partial);
+                     eps, partial);
   hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, st, partial, grid, out);
   return emsa_launch_status();
 }
@@ -339,10 +350,11 @@ extern "C" int emsa_ce_semantic_fwd(const float* logits, int32_t ld, const int64
     return EMSA_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   const int c4 = (n_classes + 3) / 4;
-  const float e = label_smoothing, ws = weights_sum;
-  if (c4 <= 4) return launch_fwd<4>(logits, ld, target, weights, n_classes, pixels, e, ws, partial, out, st);
-  if (c4 <= 10) return launch_fwd<10>(logits, ld, target, weights, n_classes, pixels, e, ws, partial, out, st);
-  return launch_fwd<16>(logits, ld, target, weights, n_classes, pixels, e, ws, partial, out, st);
+  const float e = label_smoothing;
+  (void)weights_sum;     // the forward sums w_c * -log p_c term by term; the backward needs the sum
+  if (c4 <= 4) return launch_fwd<4>(logits, ld, target, weights, n_classes, pixels, e, partial, out, st);
+  if (c4 <= 10) return launch_fwd<10>(logits, ld, target, weights, n_classes, pixels, e, partial, out, st);
+  return launch_fwd<16>(logits, ld, target, weights, n_classes, pixels, e, partial, out, st);
 }
 
 extern "C" int emsa_ce_semantic_bwd(const float* logits, int32_t ld, const int64_t* target,

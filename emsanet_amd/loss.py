@@ -21,6 +21,13 @@ Training losses on device: what `task_helper.training_step` +
 
 Arithmetic runs in libemsanet_hip.so (csrc/loss.hip): logits are read once in forward and once in
 backward; reductions are deterministic (fixed order, fp64 final sums).
+
+Labels of the cross-entropy losses: 1..n_classes are classes, 0 is void.  Every other value -- a
+label above n_classes (255 in a uint8 map) or a negative one -- is treated exactly like void: the
+pixel adds nothing to the loss or its divisor and its gradient row is zero; no error is raised.
+A map without a single valid label gives loss 0 and an all-zero gradient.  More than 64 classes,
+a target whose element count differs from the logits' pixels and instance targets of another
+size than the predictions raise `EmsaError`.
 """
 import torch
 from torch.autograd import Function
@@ -36,6 +43,13 @@ class SemanticCEFunction(Function):
     def forward(ctx, logits, target, weights, label_smoothing, weights_sum):
         logits = Fn.as_act(logits)
         n, c, h, w = logits.shape
+        ld = Fn.ld_of(logits)
+        if ld % 4 or logits.data_ptr() % 16:
+            # the kernel reads 16-byte chunks of a pixel's row: a class count off the multiples of
+            # 4 stored densely, or a slice that starts inside a chunk, is staged in padded rows
+            # (ld is kept: a single pixel's view does not tell its row length)
+            ld = Fn.pad4(c)
+            logits = Fn.copy_channels(logits, Fn.act_empty(n, c, h, w, logits.device, ld=ld))
         if target.dtype != torch.int64:
             target = target.long()
         target = target.contiguous()
@@ -46,12 +60,13 @@ class SemanticCEFunction(Function):
         partial = Fn._empty((2 * L.emsa_ce_semantic_blocks(pixels),), logits.device)
         out = Fn._empty((2,), logits.device)
         weights = weights.detach().float().contiguous()
-        check(L.emsa_ce_semantic_fwd(logits.data_ptr(), Fn.ld_of(logits), target.data_ptr(),
+        check(L.emsa_ce_semantic_fwd(logits.data_ptr(), ld, target.data_ptr(),
                                      weights.data_ptr(), c, pixels, label_smoothing, weights_sum,
                                      partial.data_ptr(), out.data_ptr(), Fn._stream()),
               'emsa_ce_semantic_fwd')
         ctx.save_for_backward(logits, target, weights, out)
         ctx.smoothing = (label_smoothing, weights_sum)
+        ctx.ld = ld
         return out[0]
 
     @staticmethod
@@ -62,7 +77,7 @@ class SemanticCEFunction(Function):
         d = Fn.act_empty(n, Fn.pad4(c), h, w, logits.device)
         g = gout.detach().float().reshape(1).contiguous()
         eps, wsum = ctx.smoothing
-        check(_lib.lib().emsa_ce_semantic_bwd(logits.data_ptr(), Fn.ld_of(logits),
+        check(_lib.lib().emsa_ce_semantic_bwd(logits.data_ptr(), ctx.ld,
                                               target.data_ptr(), weights.data_ptr(), c,
                                               n * h * w, eps, wsum, out.data_ptr(), g.data_ptr(),
                                               d.data_ptr(), Fn.ld_of(d), Fn._stream()),
@@ -131,7 +146,12 @@ class InstanceLossFunction(Function):
         ogt = offset_gt.float().permute(0, 2, 3, 1).contiguous()        # [pixels][2]
         rgt = orient_gt.reshape(-1).float().contiguous() if has_o else None
         cm, fgm, fgo = u8(center_mask), u8(fg), u8(fg_orient) if has_o else None
-        if cgt.numel() != pixels or ogt.numel() != 2 * pixels or fgm.numel() != pixels:
+        if tuple(offset.shape) != (n, 2, h, w) or (has_o and tuple(orient.shape) != (n, 2, h, w)):
+            raise _lib.EmsaError("instance loss: centre, offset and orientation predictions "
+                                 "differ in size")
+        if cgt.numel() != pixels or ogt.numel() != 2 * pixels or fgm.numel() != pixels or \
+                (cm is not None and cm.numel() != pixels) or \
+                (has_o and (rgt.numel() != pixels or fgo.numel() != pixels)):
             raise _lib.EmsaError("instance loss: target shapes do not match the predictions")
         L = _lib.lib()
         partial = Fn._empty((6 * L.emsa_instance_loss_blocks(pixels),), dev)
