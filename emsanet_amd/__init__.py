@@ -12,4 +12,7 @@ def __getattr__(name):
     if name == 'get_decoders':
         from .decoder import get_decoders
         return get_decoders
+    if name in ('MeanIntersectionOverUnion', 'PanopticQuality', 'panoptic_targets'):
+        from . import metrics
+        return getattr(metrics, name)
     raise AttributeError(name)

@@ -1,0 +1,227 @@
+# -*- coding: utf-8 -*-
+"""
+Validation metrics on device: mean IoU and panoptic quality, the two values the reference keeps its
+checkpoints by (`valid_semantic_miou`, `valid_panoptic_all_deeplab_pq`: /root/reference/main.py:229,
+emsanet/args.py:1054).
+
+The reference takes them from `metric.MeanIntersectionOverUnion` / `metric.PanopticQuality` of the
+un-vendored `nicr_mt_scene_analysis` library.  The classes here keep that surface
+(/root/reference/external/stuff/eval_miou.py:39-67, emsanet/tests/test_metrics_with_model.py:82-88,
+186-237) and count on the GPU, where the post-processed maps already are: `update()` only launches
+kernels on the current stream (no device-to-host copy, no synchronisation, no allocation after the
+first call for a shape, so it can be captured into a graph); the one host read is in `compute()`.
+Arithmetic: csrc/metrics.hip -- integer sums only, so results are independent of the execution order.
+"""
+import torch
+
+from . import _lib
+from ._lib import check
+from .functional import _stream
+from .postprocessing import thing_table
+
+_LABEL_DTYPES = {torch.int64: 0, torch.int32: 1, torch.uint8: 2}       # EMSA_LABEL_*
+IOU_ONE = 1 << 40                                                      # fixed point of iou_sum
+
+
+def _label_map(t, name, what):
+    if not torch.is_tensor(t):
+        raise TypeError(f"{name}: {what} must be a tensor")
+    if not t.is_cuda:
+        raise NotImplementedError(f"{name}: {what} is a CPU tensor; the metrics count on the GPU only")
+    if t.dtype not in _LABEL_DTYPES:
+        raise TypeError(f"{name}: {what} has dtype {t.dtype}; int64, int32 or uint8 label maps only")
+    return t.contiguous()
+
+
+class MeanIntersectionOverUnion:
+    """[U] restatement of the library's `MeanIntersectionOverUnion(n_classes, ignore_first_class)`
+    (the upstream class is not vendored; surface as /root/reference/external/stuff/eval_miou.py:39-67
+    uses it).  `update(preds, targets)` adds the label maps (equal shapes; int64 / int32 / uint8) into
+    the confusion matrix cm[target][pred]; `compute()` is the mean of
+    IoU_c = cm[c][c] / (row_c + col_c - cm[c][c]) over the classes with a non-zero union, after row
+    and column 0 (void) have been dropped when `ignore_first_class`.  A label outside [0, n_classes)
+    is not counted and makes `compute()` raise."""
+
+    def __init__(self, n_classes, ignore_first_class=False):
+        if n_classes < 1 + int(bool(ignore_first_class)):
+            raise ValueError(f"MeanIntersectionOverUnion: n_classes={n_classes}")
+        self.n_classes = int(n_classes)
+        self.ignore_first_class = bool(ignore_first_class)
+        self._state = None                      # int64 [C*C + 1]: the matrix, then n_invalid
+
+    def _buffers(self, device):
+        if self._state is None or self._state.device != device:
+            self._state = torch.zeros(self.n_classes ** 2 + 1, device=device, dtype=torch.int64)
+        return self._state
+
+    def update(self, preds, targets):
+        p = _label_map(preds, 'MeanIntersectionOverUnion.update', 'preds')
+        t = _label_map(targets, 'MeanIntersectionOverUnion.update', 'targets')
+        if p.numel() != t.numel() or p.device != t.device:
+            raise ValueError(f"MeanIntersectionOverUnion.update: preds {tuple(p.shape)} on {p.device} vs "
+                             f"targets {tuple(t.shape)} on {t.device}")
+        s = self._buffers(p.device)
+        cc = self.n_classes ** 2
+        check(_lib.lib().emsa_confusion_matrix(
+            p.data_ptr(), _LABEL_DTYPES[p.dtype], t.data_ptr(), _LABEL_DTYPES[t.dtype], p.numel(),
+            self.n_classes, s.data_ptr(), s.data_ptr() + 8 * cc, _stream()), 'emsa_confusion_matrix')
+
+    @property
+    def confusion_matrix(self):
+        """(C, C) int64 on the device, [target][pred] (a view of the running state: no sync)"""
+        if self._state is None:
+            return torch.zeros((self.n_classes, self.n_classes), dtype=torch.int64)
+        return self._state[:-1].view(self.n_classes, self.n_classes)
+
+    def reset(self):
+        if self._state is not None:
+            self._state.zero_()
+
+    def compute(self):
+        if self._state is None:
+            return 0.0
+        s = self._state.cpu()
+        if int(s[-1]) != 0:
+            raise ValueError(f"MeanIntersectionOverUnion: n_invalid = {int(s[-1])} pixels carried a label "
+                             f"outside [0, {self.n_classes}) and were not counted")
+        cm = s[:-1].view(self.n_classes, self.n_classes)
+        if self.ignore_first_class:
+            cm = cm[1:, 1:]
+        tp = cm.diagonal()
+        union = cm.sum(0) + cm.sum(1) - tp
+        keep = union > 0
+        if not bool(keep.any()):
+            return 0.0
+        return float((tp[keep].double() / union[keep].double()).mean())
+
+
+class PanopticQuality:
+    """`metric.PanopticQuality(num_categories, ignored_label, max_instances_per_category, offset,
+    is_thing)` as /root/reference/emsanet/tests/test_metrics_with_model.py:82-88 builds it, with the
+    DeepLab2 / panopticapi rules that test holds the library to (at 9 decimals).
+
+    `update(preds, targets)`: int64 panoptic id maps (N, H, W) on the GPU,
+    id = category * max_instances_per_category + instance (`panoptic_segmentation_deeplab[_fullres]`
+    and `panoptic_targets`).  Per image, a predicted and a target segment of one category (not the
+    ignored one) match iff IoU > 1/2, where the prediction's overlap with ignored target pixels is
+    left out of the union; a match is a tp, an unmatched target a fn, an unmatched prediction a fp
+    unless more than half of it lies on ignored pixels.
+
+    `compute()` -> dict all_pq / all_sq / all_rq, things_*, stuff_*: per category
+    sq = iou_sum / tp, rq = tp / (tp + fn/2 + fp/2), pq = sq * rq, averaged over the categories of the
+    group with tp + fn + fp > 0 (0.0 for a group without any).
+
+    `offset` is accepted for interface compatibility and unused: the device never forms id products.
+    `max_segments` bounds the distinct segments per side per image; more make `compute()` raise."""
+
+    def __init__(self, num_categories, ignored_label, max_instances_per_category, offset=None,
+                 is_thing=None, max_segments=256):
+        if is_thing is None or len(is_thing) != num_categories:
+            raise ValueError("PanopticQuality: is_thing must name every one of the num_categories")
+        if max_instances_per_category < 1:
+            raise ValueError("PanopticQuality: max_instances_per_category must be positive")
+        self.num_categories = int(num_categories)
+        self.ignored_label = int(ignored_label)
+        self.max_instances_per_category = int(max_instances_per_category)
+        self.offset = offset
+        self.is_thing = tuple(bool(t) for t in is_thing)
+        self.max_segments = int(max_segments)
+        if _lib.lib().emsa_panoptic_workspace_bytes(1, self.max_segments) <= 0:
+            raise ValueError(f"PanopticQuality: max_segments={max_segments} outside [1, 1024]")
+        self._state = None                      # int64 [4*K + 1]: tp, fn, fp, iou_sum, then 2 int32 flags
+        self._ws = {}                           # (device, images) -> workspace
+
+    def _buffers(self, device, n):
+        if self._state is None or self._state.device != device:
+            self._state = torch.zeros(4 * self.num_categories + 1, device=device, dtype=torch.int64)
+            self._ws = {}
+        ws = self._ws.get(n)
+        if ws is None:
+            nbytes = _lib.lib().emsa_panoptic_workspace_bytes(n, self.max_segments)
+            ws = self._ws[n] = torch.empty(nbytes, device=device, dtype=torch.uint8)
+        return self._state, ws
+
+    def update(self, preds, targets):
+        for what, t in (('preds', preds), ('targets', targets)):
+            if not torch.is_tensor(t):
+                raise TypeError(f"PanopticQuality.update: {what} must be a tensor")
+            if not t.is_cuda:
+                raise NotImplementedError(f"PanopticQuality.update: {what} is a CPU tensor; the metrics "
+                                          "count on the GPU only")
+            if t.dtype != torch.int64:
+                raise TypeError(f"PanopticQuality.update: {what} has dtype {t.dtype}; int64 panoptic ids only")
+        if preds.shape != targets.shape or preds.dim() not in (2, 3) or preds.device != targets.device:
+            raise ValueError(f"PanopticQuality.update: preds {tuple(preds.shape)} vs targets "
+                             f"{tuple(targets.shape)}; (N, H, W) or (H, W) maps of equal shape")
+        p, t = preds.contiguous(), targets.contiguous()
+        n = 1 if p.dim() == 2 else p.shape[0]
+        hw = p.shape[-2] * p.shape[-1]
+        s, ws = self._buffers(p.device, n)
+        k = self.num_categories
+        base, flags = s.data_ptr(), s.data_ptr() + 8 * 4 * k
+        L = _lib.lib()
+        check(L.emsa_panoptic_pairs(p.data_ptr(), t.data_ptr(), n, hw, self.max_segments, ws.data_ptr(),
+                                    flags, _stream()), 'emsa_panoptic_pairs')
+        check(L.emsa_panoptic_match(ws.data_ptr(), n, self.max_segments, k, self.ignored_label,
+                                    self.max_instances_per_category, base, base + 8 * k,
+                                    base + 16 * k, base + 24 * k, flags, _stream()),
+              'emsa_panoptic_match')
+
+    def reset(self):
+        if self._state is not None:
+            self._state.zero_()
+
+    def counts(self):
+        """host copy of the state: dict tp / fn / fp / iou_sum (lists of Python ints, iou_sum in
+        units of 2^-40) -- raises like `compute()`"""
+        k = self.num_categories
+        if self._state is None:
+            return {key: [0] * k for key in ('tp', 'fn', 'fp', 'iou_sum')}
+        s = self._state.cpu()
+        overflow, invalid = (int(v) for v in s[4 * k:].view(torch.int32)[:2])
+        if overflow:
+            raise ValueError(f"PanopticQuality: segment table overflow -- an image had more than "
+                             f"max_segments = {self.max_segments} distinct segments on one side")
+        if invalid:
+            raise ValueError("PanopticQuality: invalid panoptic id -- negative, or of a category outside "
+                             f"[0, {k})")
+        v = s[:4 * k].view(4, k).tolist()
+        return {'tp': v[0], 'fn': v[1], 'fp': v[2], 'iou_sum': v[3]}
+
+    def compute(self):
+        c = self.counts()
+        groups = {'all': [], 'things': [], 'stuff': []}
+        for cat in range(self.num_categories):
+            tp, fn, fp = c['tp'][cat], c['fn'][cat], c['fp'][cat]
+            if cat == self.ignored_label or tp + fn + fp == 0:
+                continue
+            sq = (c['iou_sum'][cat] / IOU_ONE) / tp if tp else 0.0
+            rq = tp / (tp + 0.5 * fn + 0.5 * fp)
+            for g in ('all', 'things' if self.is_thing[cat] else 'stuff'):
+                groups[g].append((sq * rq, sq, rq))
+        out = {}
+        for g, rows in groups.items():
+            for j, key in enumerate(('pq', 'sq', 'rq')):
+                out[f'{g}_{key}'] = sum(r[j] for r in rows) / len(rows) if rows else 0.0
+        return out
+
+
+def panoptic_targets(semantic, instance, is_thing, label_divisor):
+    """ground-truth side of the panoptic merge, as `deeplab_merge_batch(semantic, instance, instance !=
+    0, label_divisor, np.where(is_thing)[0], 0)` is called in
+    /root/reference/emsanet/tests/test_metrics_with_model.py:155-163: semantic (labels WITH void,
+    0 = void) and instance maps of equal shape (int64 / int32 / uint8) on the GPU -> int64 ids
+    sem * label_divisor + inst for a thing class, sem * label_divisor for a stuff class, 0 for void.
+    `is_thing` is indexed by the label with void.  One kernel on the current stream, no host sync (the
+    is-thing table is uploaded once per class list: call it once before capturing a graph)."""
+    s = _label_map(semantic, 'panoptic_targets', 'semantic')
+    i = _label_map(instance, 'panoptic_targets', 'instance')
+    if s.shape != i.shape or s.device != i.device:
+        raise ValueError(f"panoptic_targets: semantic {tuple(s.shape)} vs instance {tuple(i.shape)}")
+    table = thing_table(is_thing, s.device)
+    out = torch.empty(s.shape, device=s.device, dtype=torch.int64)
+    check(_lib.lib().emsa_panoptic_targets(s.data_ptr(), _LABEL_DTYPES[s.dtype], i.data_ptr(),
+                                           _LABEL_DTYPES[i.dtype], table.data_ptr(), len(is_thing),
+                                           int(label_divisor), s.numel(), out.data_ptr(), _stream()),
+          'emsa_panoptic_targets')
+    return out

@@ -518,6 +518,52 @@ int emsa_normalize_depth(const uint16_t* depth, float* out, int64_t total, float
                          int32_t keep_zero, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Validation metrics (csrc/metrics.hip): the counting behind `valid_semantic_miou` and
+ * `valid_panoptic_all_deeplab_pq` (/root/reference/main.py:229, emsanet/args.py:1054).  Integer
+ * atomics throughout: results do not depend on the execution order.  Every entry ADDS into its
+ * result buffers (the caller zeroes them when a new evaluation starts).
+ *   emsa_confusion_matrix   cm[target][pred] += 1 over n pixels; pred / target in the label type
+ *                           named by EMSA_LABEL_*; cm int64[C][C].  A pixel with a label outside
+ *                           [0, C) is not counted: *n_invalid += 1 instead.  Per-workgroup LDS bins
+ *                           while C*C*4 bytes <= 48 KiB (C <= 110), global atomics above.
+ *   emsa_panoptic_targets   ground-truth panoptic ids: out = sem * label_divisor + (is_thing[sem] ?
+ *                           inst : 0), 0 for void (sem == 0) and for sem outside [0, n_classes);
+ *                           is_thing uint8[n_classes] (DEVICE), indexed by the label WITH void
+ *                           (emsanet/tests/test_metrics_with_model.py:155-163)
+ *   emsa_panoptic_pairs     per image (pred / target int64[n_images][hw], id = category *
+ *                           max_instances_per_category + instance): the distinct segments of either
+ *                           side and the pixel count of every (target, predicted) pair, into
+ *                           `workspace` (emsa_panoptic_workspace_bytes(n_images, max_segments) bytes,
+ *                           cleared by the call).  max_segments <= 1024 bounds the segments per side
+ *                           per image; more set flags[0], a negative id sets flags[1]; such pixels
+ *                           are dropped, nothing is written out of bounds.
+ *   emsa_panoptic_match     DeepLab2 / panopticapi matching on that workspace, per image: for every
+ *                           pair of equal category != ignored_label, union = area_t + area_p - inter
+ *                           - void_p (void_p = overlap of the prediction with targets of the ignored
+ *                           category); match iff 2*inter > union: tp[cat] += 1, iou_sum[cat] +=
+ *                           round(inter/union * 2^40).  Unmatched target: fn[cat] += 1; unmatched
+ *                           prediction: fp[cat] += 1 unless 2*void_p > area_p.  tp / fn / fp /
+ *                           iou_sum int64[num_categories]; a category >= num_categories sets
+ *                           flags[1] and the segment is skipped.  flags int32[2] (DEVICE).
+ * ------------------------------------------------------------------------------------------ */
+#define EMSA_LABEL_I64 0
+#define EMSA_LABEL_I32 1
+#define EMSA_LABEL_U8 2
+int emsa_confusion_matrix(const void* pred, int32_t pred_dtype, const void* target,
+                          int32_t target_dtype, int64_t n, int32_t n_classes, int64_t* cm,
+                          int64_t* n_invalid, void* stream);
+int emsa_panoptic_targets(const void* semantic, int32_t semantic_dtype, const void* instance,
+                          int32_t instance_dtype, const uint8_t* is_thing, int32_t n_classes,
+                          int64_t label_divisor, int64_t n, int64_t* out, void* stream);
+int64_t emsa_panoptic_workspace_bytes(int32_t n_images, int32_t max_segments);
+int emsa_panoptic_pairs(const int64_t* pred, const int64_t* target, int32_t n_images, int64_t hw,
+                        int32_t max_segments, void* workspace, int32_t* flags, void* stream);
+int emsa_panoptic_match(const void* workspace, int32_t n_images, int32_t max_segments,
+                        int32_t num_categories, int32_t ignored_label,
+                        int64_t max_instances_per_category, int64_t* tp, int64_t* fn, int64_t* fp,
+                        int64_t* iou_sum, int32_t* flags, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Optimizer step over one flat bucket: torch.optim.SGD(momentum, weight_decay,
  * nesterov=True) as the reference configures it (emsanet/optimizer.py:29-36), one pass:
  *   d = grad * grad_scale + weight_decay * p;  buf = first_step ? d : momentum * buf + d;
