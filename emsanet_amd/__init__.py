@@ -15,4 +15,7 @@ def __getattr__(name):
     if name in ('MeanIntersectionOverUnion', 'PanopticQuality', 'panoptic_targets'):
         from . import metrics
         return getattr(metrics, name)
+    if name in ('TrainingTargetGenerator', 'orientation_table'):
+        from . import targets
+        return getattr(targets, name)
     raise AttributeError(name)

@@ -44,8 +44,15 @@ class EmsaConvGeom(Structure):
     ]
 
 
+class EmsaTargetScale(Structure):
+    _fields_ = [('scale', c_int32), ('sigma', c_int32), ('semantic', c_void_p), ('center', c_void_p),
+                ('offset', c_void_p), ('foreground', c_void_p), ('orientation', c_void_p),
+                ('orientation_foreground', c_void_p)]
+
+
 _P = c_void_p          # device pointers travel as integers (tensor.data_ptr())
 _GP = POINTER(EmsaConvGeom)
+_TP = POINTER(EmsaTargetScale)
 
 # name -> (restype, argtypes); must stay in sync with include/emsanet_hip.h (tests check it)
 SIGNATURES = {
@@ -158,6 +165,13 @@ SIGNATURES = {
     'emsa_panoptic_pairs': (c_int, [_P, _P, c_int32, c_int64, c_int32, _P, _P, _P]),
     'emsa_panoptic_match': (c_int, [_P, c_int32, c_int32, c_int32, c_int32, c_int64, _P, _P, _P, _P,
                                     _P, _P]),
+    'emsa_targets_workspace_bytes': (c_int64, [c_int32, c_int32, c_int32]),
+    'emsa_targets_table_entries': (c_int, [c_int32]),
+    'emsa_targets_stats': (c_int, [_P, c_int32, _P, c_int32, _P, c_int32, c_int32, c_int32, c_int32, _TP,
+                                   c_int32, c_int32, _P, _P]),
+    'emsa_targets_finalize': (c_int, [c_int32, c_int32, c_int32, _TP, c_int32, c_int32, _P, _P]),
+    'emsa_targets_render': (c_int, [_P, c_int32, _P, c_int32, _P, _P, _P, c_int32, c_int32, c_int32,
+                                    c_int32, _TP, c_int32, c_int32, c_int32, _P, _P, _P, _P]),
     'emsa_normalize_rgb': (c_int, [_P, _P, c_int32, c_int32, c_int32, c_float, _P, _P, _P]),
     'emsa_normalize_depth': (c_int, [_P, _P, c_int64, c_float, c_float, c_int32, _P]),
     'emsa_sgd_nesterov': (c_int, [_P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_int32,

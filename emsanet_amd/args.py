@@ -63,6 +63,7 @@ _DEFAULTS = {
     'normal_decoder_n_channels': ((512, 256, 128), 586),
     'normal_decoder_downsamplings': ((16, 8, 4), 597),
     'normal_decoder_upsampling': ('learned-3x3-zeropad', 606),
+    'instance_center_sigma': (8, 459),
     'instance_center_heatmap_threshold': (0.1, 469),
     'instance_center_heatmap_nms_kernel_size': (17, 478),
     'instance_center_heatmap_apply_foreground_mask': (False, 487),

@@ -13,6 +13,9 @@ MI355X-side replacement for that copy:
     run as kernels on the compute stream (`postprocessing.normalize_*`) when the batch is handed
     out, so nothing but events crosses between the streams.
 Float tensors in the incoming dict (already normalised inputs, targets) are staged as they are.
+With a `target_generator` (`emsanet_amd.targets.TrainingTargetGenerator`) the loader ships the raw
+'semantic' / 'instance' label maps (plus 'orientations', 'scene') and the training targets are
+generated from the staged maps on the compute stream, under 'targets'.
 """
 from typing import Dict, Iterable, Iterator
 
@@ -27,10 +30,12 @@ class BatchStager:
 
     depth_stats = (mean, std) of the depth normalisation; `ring` device buffer sets: a set is
     refilled (on the copy stream) as soon as the kernels that read its previous content have been
-    enqueued.  Non-tensor entries of a batch are passed through."""
+    enqueued.  Non-tensor entries of a batch are passed through.  target_generator: when given, its
+    `generate` runs over the staged label maps of every batch and the result is handed out under
+    'targets' (its own ring must be at least as deep as the number of batches the caller keeps)."""
 
     def __init__(self, host_batches: Iterable[Dict], device, depth_stats=(0.0, 1.0), ring: int = 2,
-                 rgb_key: str = 'rgb', depth_key: str = 'depth'):
+                 rgb_key: str = 'rgb', depth_key: str = 'depth', target_generator=None):
         self.device = torch.device(device)
         if self.device.type != 'cuda':
             raise _lib.EmsaError(f"BatchStager stages batches onto an AMD GPU, not onto {self.device}")
@@ -40,6 +45,7 @@ class BatchStager:
         self.depth_stats = depth_stats
         self.ring = ring
         self.rgb_key, self.depth_key = rgb_key, depth_key
+        self.target_generator = target_generator
         self.copy_stream = torch.cuda.Stream(device=self.device)
         self._slots = [dict(bufs={}, copied=torch.cuda.Event(), freed=None) for _ in range(ring)]
         self.bytes_staged = 0
@@ -84,6 +90,9 @@ class BatchStager:
             else:
                 # handed out as is: it must not be overwritten while the step uses it
                 out[k] = raw.clone()
+        if self.target_generator is not None:
+            # reads the raw buffers on the compute stream: covered by the `freed` event below
+            out['targets'] = self.target_generator.generate({k: slot['bufs'][k] for k in slot['keys']})
         ev = torch.cuda.Event()
         ev.record(cur)           # every reader of the raw buffers has been enqueued before this
         slot['freed'] = ev

@@ -564,6 +564,60 @@ int emsa_panoptic_match(const void* workspace, int32_t n_images, int32_t max_seg
                         int64_t* iou_sum, int32_t* flags, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Training targets (csrc/targets.hip): the per-scale targets of emsanet_amd.loss.TrainingLosses from
+ * the raw label maps of a batch -- what /root/reference/emsanet/preprocessing.py:89-104,156-213 runs
+ * on the CPU in the data-loader workers.  Rules: emsanet_amd/targets.py.
+ * semantic / instance: (n, h, w) label maps in the type named by EMSA_LABEL_* (0 = void / no
+ * instance); is_thing, use_orientation uint8[n_classes] (DEVICE), indexed by the label WITH void.
+ * `scales` is a HOST array of n_scales <= EMSA_TARGETS_MAX_SCALES entries, read during the call;
+ * h and w must be multiples of every scale (EMSA_E_SHAPE otherwise).  An entry with center == NULL
+ * gets the down-scaled semantic map only; one with semantic == NULL the instance targets only.
+ * Outputs of scale s are dense (n, h/s, w/s) maps; `offset` holds (dy, dx) per pixel, i.e. is
+ * (n, h/s, w/s, 2) in memory.  `sigma` in [1, 16] where center != NULL.
+ *   emsa_targets_workspace_bytes  bytes of `workspace` (the caller zeroes it ONCE; every finalize
+ *                                 leaves it ready for the next stats)
+ *   emsa_targets_table_entries    2 * (3 * sigma + 1)^2 + 1: entries of one Gaussian table,
+ *                                 table[d2] = exp(-d2 / (2 sigma^2)) rounded to fp32
+ *   emsa_targets_stats            count / sum_y / sum_x per (scale, image, id) into the workspace
+ *   emsa_targets_finalize         centres = round-half-even(sum / count), in integers, a compact
+ *                                 centre list per (scale, image); the sums are zero again
+ *   emsa_targets_render           every output of every scale.  gauss_tables (DEVICE): the tables of
+ *                                 the scales with center != NULL, one after the other in scale order.
+ *                                 orientations float[n][max_instances] (DEVICE, NaN = none) or NULL;
+ *                                 instance may be NULL when no scale has center != NULL.
+ *                                 An id outside [0, max_instances) sets flags[0], a label outside
+ *                                 [0, n_classes) flags[1] (int32[2], DEVICE); such a pixel counts as
+ *                                 having no instance.
+ * max_instances in [2, 1024].
+ * ------------------------------------------------------------------------------------------ */
+#define EMSA_LABEL_I16 3
+#define EMSA_LABEL_U16 4
+#define EMSA_TARGETS_MAX_SCALES 8
+typedef struct EmsaTargetScale {
+  int32_t scale, sigma;
+  int64_t* semantic;
+  float* center;
+  float* offset;
+  uint8_t* foreground;
+  float* orientation;
+  uint8_t* orientation_foreground;
+} EmsaTargetScale;
+int64_t emsa_targets_workspace_bytes(int32_t n_images, int32_t n_scales, int32_t max_instances);
+int emsa_targets_table_entries(int32_t sigma);
+int emsa_targets_stats(const void* semantic, int32_t semantic_dtype, const void* instance,
+                       int32_t instance_dtype, const uint8_t* is_thing, int32_t n_classes, int32_t n,
+                       int32_t h, int32_t w, const EmsaTargetScale* scales, int32_t n_scales,
+                       int32_t max_instances, void* workspace, void* stream);
+int emsa_targets_finalize(int32_t n, int32_t h, int32_t w, const EmsaTargetScale* scales,
+                          int32_t n_scales, int32_t max_instances, void* workspace, void* stream);
+int emsa_targets_render(const void* semantic, int32_t semantic_dtype, const void* instance,
+                        int32_t instance_dtype, const float* orientations, const uint8_t* is_thing,
+                        const uint8_t* use_orientation, int32_t n_classes, int32_t n, int32_t h,
+                        int32_t w, const EmsaTargetScale* scales, int32_t n_scales,
+                        int32_t max_instances, int32_t normalized_offset, const float* gauss_tables,
+                        void* workspace, int32_t* flags, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Optimizer step over one flat bucket: torch.optim.SGD(momentum, weight_decay,
  * nesterov=True) as the reference configures it (emsanet/optimizer.py:29-36), one pass:
  *   d = grad * grad_scale + weight_decay * p;  buf = first_step ? d : momentum * buf + d;
