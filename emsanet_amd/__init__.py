@@ -18,4 +18,7 @@ def __getattr__(name):
     if name in ('TrainingTargetGenerator', 'orientation_table'):
         from . import targets
         return getattr(targets, name)
+    if name == 'TrainingAugmenter':
+        from .augment import TrainingAugmenter
+        return TrainingAugmenter
     raise AttributeError(name)

@@ -172,6 +172,10 @@ SIGNATURES = {
     'emsa_targets_finalize': (c_int, [c_int32, c_int32, c_int32, _TP, c_int32, c_int32, _P, _P]),
     'emsa_targets_render': (c_int, [_P, c_int32, _P, c_int32, _P, _P, _P, c_int32, c_int32, c_int32,
                                     c_int32, _TP, c_int32, c_int32, c_int32, _P, _P, _P, _P]),
+    'emsa_augment_params': (c_int, [_P, _P] + [c_int32] * 7 + [c_int64, c_float, c_float, c_float, _P]),
+    'emsa_augment_apply': (c_int, [_P, _P, _P, c_int32, _P, c_int32, _P] + [c_int32] * 5 +
+                           [_P, _P, _P, _P, c_float, _P, _P, c_float, c_float, c_int32, c_int32, _P]),
+    'emsa_augment_orientations': (c_int, [_P, _P, _P, c_int32, c_int32, _P]),
     'emsa_normalize_rgb': (c_int, [_P, _P, c_int32, c_int32, c_int32, c_float, _P, _P, _P]),
     'emsa_normalize_depth': (c_int, [_P, _P, c_int64, c_float, c_float, c_int32, _P]),
     'emsa_sgd_nesterov': (c_int, [_P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_int32,

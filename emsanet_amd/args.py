@@ -91,6 +91,9 @@ _DEFAULTS = {
     'he_init': (('encoder-fusion',), 626),
     'no_zero_init_decoder_residuals': (False, 640),
     'debug': (False, 1116),
+    # training augmentation (emsanet_amd.augment.TrainingAugmenter)
+    'aug_scale_min': (1.0, 841),
+    'aug_scale_max': (1.4, 847),
     # NOT a reference option (line 0): storage type of the engine's activations, see
     # EMSANet.set_compute_dtype ('float32' = the reference's arithmetic)
     'compute_dtype': ('float32', 0),

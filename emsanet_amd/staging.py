@@ -16,6 +16,9 @@ Float tensors in the incoming dict (already normalised inputs, targets) are stag
 With a `target_generator` (`emsanet_amd.targets.TrainingTargetGenerator`) the loader ships the raw
 'semantic' / 'instance' label maps (plus 'orientations', 'scene') and the training targets are
 generated from the staged maps on the compute stream, under 'targets'.
+With an `augmenter` (`emsanet_amd.augment.TrainingAugmenter`) the loader ships UN-AUGMENTED raw frames
+and label maps: resize, crop, HSV jitter and flip run fused with the normalisation when the batch is
+handed out, and the targets are generated from the augmented maps.
 """
 from typing import Dict, Iterable, Iterator
 
@@ -32,10 +35,14 @@ class BatchStager:
     refilled (on the copy stream) as soon as the kernels that read its previous content have been
     enqueued.  Non-tensor entries of a batch are passed through.  target_generator: when given, its
     `generate` runs over the staged label maps of every batch and the result is handed out under
-    'targets' (its own ring must be at least as deep as the number of batches the caller keeps)."""
+    'targets' (its own ring must be at least as deep as the number of batches the caller keeps).
+    augmenter: when given, its `apply` runs over the staged raw buffers instead of the two
+    normalisation kernels (it carries its own depth statistics); its outputs -- normalised inputs,
+    augmented label maps, orientation table -- are handed out and feed the target generator.  The same
+    holds for the depth of its ring."""
 
     def __init__(self, host_batches: Iterable[Dict], device, depth_stats=(0.0, 1.0), ring: int = 2,
-                 rgb_key: str = 'rgb', depth_key: str = 'depth', target_generator=None):
+                 rgb_key: str = 'rgb', depth_key: str = 'depth', target_generator=None, augmenter=None):
         self.device = torch.device(device)
         if self.device.type != 'cuda':
             raise _lib.EmsaError(f"BatchStager stages batches onto an AMD GPU, not onto {self.device}")
@@ -46,6 +53,7 @@ class BatchStager:
         self.ring = ring
         self.rgb_key, self.depth_key = rgb_key, depth_key
         self.target_generator = target_generator
+        self.augmenter = augmenter
         self.copy_stream = torch.cuda.Stream(device=self.device)
         self._slots = [dict(bufs={}, copied=torch.cuda.Event(), freed=None) for _ in range(ring)]
         self.bytes_staged = 0
@@ -81,9 +89,18 @@ class BatchStager:
         cur = torch.cuda.current_stream(self.device)
         cur.wait_event(slot['copied'])
         out = dict(slot['extra'])
+        augmented = {}
+        if self.augmenter is not None:
+            # reads the raw buffers on the compute stream: covered by the `freed` event below
+            names = {self.rgb_key: 'rgb', self.depth_key: 'depth'}
+            res = self.augmenter.apply({names.get(k, k): slot['bufs'][k] for k in slot['keys']})
+            back = {'rgb': self.rgb_key, 'depth': self.depth_key}
+            augmented = {back.get(k, k): v for k, v in res.items()}
         for k in slot['keys']:
             raw = slot['bufs'][k]
-            if k == self.rgb_key and raw.dtype == torch.uint8:
+            if k in augmented:
+                out[k] = augmented[k]
+            elif k == self.rgb_key and raw.dtype == torch.uint8:
                 out[k] = normalize_rgb(raw)
             elif k == self.depth_key and raw.dtype in (torch.uint16, torch.int16):
                 out[k] = normalize_depth(raw, *self.depth_stats)
@@ -92,7 +109,8 @@ class BatchStager:
                 out[k] = raw.clone()
         if self.target_generator is not None:
             # reads the raw buffers on the compute stream: covered by the `freed` event below
-            out['targets'] = self.target_generator.generate({k: slot['bufs'][k] for k in slot['keys']})
+            out['targets'] = self.target_generator.generate(
+                {k: augmented.get(k, slot['bufs'][k]) for k in slot['keys']})
         ev = torch.cuda.Event()
         ev.record(cur)           # every reader of the raw buffers has been enqueued before this
         slot['freed'] = ev

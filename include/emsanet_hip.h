@@ -618,6 +618,41 @@ int emsa_targets_render(const void* semantic, int32_t semantic_dtype, const void
                         void* workspace, int32_t* flags, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Training augmentation (csrc/augment.hip): random resize, crop, HSV jitter and horizontal flip of the
+ * raw frames and label maps of a batch, fused with the input normalisation -- what
+ * /root/reference/emsanet/preprocessing.py:106-123 runs on the CPU in the data-loader workers.
+ * Rules: emsanet_amd/augment.py.  Source frames are hs x ws, outputs h x w, every side <= 4096.
+ * `params` int32[n][8] (DEVICE): (Hr, Wr, cy, cx, flip, dh, ds, dv), the three deltas as float bits.
+ *   emsa_augment_params        draws the table from state = uint32 {seed, step} (DEVICE) and stores
+ *                              step + 1.  The scale numerator q (scale = q / 1024) is uniform in
+ *                              [q_min, q_max]; flip iff hash < flip_threshold (0 ... 2^32).
+ *                              EMSA_E_SHAPE if the crop does not fit the resize at q_min or the resize
+ *                              at q_max has a side above 16384.
+ *   emsa_augment_apply         rgb uint8 [n][hs][ws][3] -> out_rgb float [n][3][h][w] (integer bilinear,
+ *                              the HSV jitter if hsv != 0, then (v * rgb_scale - mean) / std as
+ *                              emsa_normalize_rgb; mean3 / std3 on the HOST); depth uint16 [n][hs][ws]
+ *                              -> out_depth float [n][1][h][w] (nearest, then as emsa_normalize_depth);
+ *                              label0 / label1 [n][hs][ws] in the type named by EMSA_LABEL_* ->
+ *                              out_label0 / out_label1 [n][h][w] in the same type (nearest).  Any input
+ *                              may be NULL together with its output.  Source indices are clamped to
+ *                              the frame whatever the table holds.
+ *   emsa_augment_orientations  float [n][max_instances]: theta -> (2 pi - theta) mod 2 pi for the
+ *                              samples whose flip is set, a copy for the others; NaN stays NaN.
+ * ------------------------------------------------------------------------------------------ */
+int emsa_augment_params(int32_t* state, int32_t* table, int32_t n, int32_t hs, int32_t ws, int32_t h,
+                        int32_t w, int32_t q_min, int32_t q_max, int64_t flip_threshold,
+                        float hue_amplitude, float saturation_amplitude, float value_amplitude,
+                        void* stream);
+int emsa_augment_apply(const uint8_t* rgb, const uint16_t* depth, const void* label0,
+                       int32_t label0_dtype, const void* label1, int32_t label1_dtype,
+                       const int32_t* params, int32_t n, int32_t hs, int32_t ws, int32_t h, int32_t w,
+                       float* out_rgb, float* out_depth, void* out_label0, void* out_label1,
+                       float rgb_scale, const float* mean3, const float* std3, float depth_mean,
+                       float depth_std, int32_t keep_zero, int32_t hsv, void* stream);
+int emsa_augment_orientations(const float* orientations, float* out, const int32_t* params, int32_t n,
+                              int32_t max_instances, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Optimizer step over one flat bucket: torch.optim.SGD(momentum, weight_decay,
  * nesterov=True) as the reference configures it (emsanet/optimizer.py:29-36), one pass:
  *   d = grad * grad_scale + weight_decay * p;  buf = first_step ? d : momentum * buf + d;
