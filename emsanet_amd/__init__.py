@@ -12,12 +12,16 @@ def __getattr__(name):
     if name == 'get_decoders':
         from .decoder import get_decoders
         return get_decoders
-    if name in ('MeanIntersectionOverUnion', 'PanopticQuality', 'panoptic_targets'):
+    if name in ('MeanIntersectionOverUnion', 'PanopticQuality', 'panoptic_targets', 'SceneAccuracy',
+                'MeanAbsoluteAngularError'):
         from . import metrics
         return getattr(metrics, name)
     if name in ('TrainingTargetGenerator', 'orientation_table'):
         from . import targets
         return getattr(targets, name)
+    if name == 'ValidationEvaluator':
+        from .evaluation import ValidationEvaluator
+        return ValidationEvaluator
     if name == 'TrainingAugmenter':
         from .augment import TrainingAugmenter
         return TrainingAugmenter

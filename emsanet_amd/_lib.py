@@ -165,6 +165,10 @@ SIGNATURES = {
     'emsa_panoptic_pairs': (c_int, [_P, _P, c_int32, c_int64, c_int32, _P, _P, _P]),
     'emsa_panoptic_match': (c_int, [_P, c_int32, c_int32, c_int32, c_int32, c_int64, _P, _P, _P, _P,
                                     _P, _P]),
+    'emsa_panoptic_match_pairs': (c_int, [_P, c_int32, c_int32, c_int32, c_int32, c_int64, _P, _P, _P,
+                                          _P, _P, _P, _P, _P]),
+    'emsa_angular_error': (c_int, [_P, _P, _P, c_int32, c_int32, _P, c_int32, _P, _P, c_int32, c_int64,
+                                   _P, _P, _P]),
     'emsa_targets_workspace_bytes': (c_int64, [c_int32, c_int32, c_int32]),
     'emsa_targets_table_entries': (c_int, [c_int32]),
     'emsa_targets_stats': (c_int, [_P, c_int32, _P, c_int32, _P, c_int32, c_int32, c_int32, c_int32, _TP,

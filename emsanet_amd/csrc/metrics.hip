@@ -4,7 +4,11 @@
 // eval post-processing; counting them there is one pass over 8 + 8 bytes per pixel.
 //  * confusion matrix cm[target][pred] of two label maps (int64 / int32 / uint8)
 //  * panoptic quality (Kirillov et al., CVPR 2019) by the DeepLab2 / panopticapi rules: per image
-//    the pixel count of every (target segment, predicted segment) pair, then the matching
+//    the pixel count of every (target segment, predicted segment) pair, then the matching --
+//    optionally with the list of matched (predicted id, target id) pairs written out
+//  * angular error of per-instance mean orientations against a ground-truth angle table, over the
+//    instance slots or over such a match list (`valid_orientation_mae_gt_deg`,
+//    `valid_panoptic_mae_deeplab_deg`)
 // Every sum is an integer taken with integer atomics: no result depends on the execution order.
 #include "common.h"
 
@@ -242,17 +246,24 @@ __device__ __forceinline__ unsigned long long iou_fixed40(unsigned long long int
   return (q1 << 20) + q2 + (2ull * r2 >= uni ? 1ull : 0ull);
 }
 
-// one workgroup per image; thread = predicted slot, loop = target slots (coalesced matrix rows)
+// one workgroup per image; thread = predicted slot, loop = target slots (coalesced matrix rows).
+// EXPORT: every match is also written as (predicted id, target id) into the image's list
+// matches[img][T][2]; a slot of the list is claimed by an LDS counter (first come first: the order
+// inside the list is unspecified), the counter ends up in n_matches[img].  A target matches at most
+// one prediction (IoU > 1/2), so an image has at most T matches.
+template <bool EXPORT>
 __global__ __launch_bounds__(kThreads) void panoptic_match_kernel(
     const unsigned char* __restrict__ workspace, int T, int num_categories, int ignored,
     long max_inst, unsigned long long* __restrict__ tp, unsigned long long* __restrict__ fn,
     unsigned long long* __restrict__ fp, unsigned long long* __restrict__ iou_sum,
-    int32_t* __restrict__ flags) {
+    int32_t* __restrict__ flags, int64_t* __restrict__ matches, int32_t* __restrict__ n_matches) {
   // category of a slot: -1 free, -2 outside [0, num_categories)
   __shared__ int cat_t[kMaxSegments], cat_p[kMaxSegments];
   __shared__ int area_t[kMaxSegments], area_p[kMaxSegments], void_p[kMaxSegments];
   __shared__ int hit_t[kMaxSegments], hit_p[kMaxSegments];
+  __shared__ int s_matches;
   const int tid = threadIdx.x;
+  if (EXPORT && tid == 0) s_matches = 0;       // (visible after the first barrier below)
   const unsigned char* ws = workspace + (long)blockIdx.x * pan_image_bytes(T);
   const unsigned long long* keys_t = (const unsigned long long*)ws;
   const unsigned long long* keys_p = keys_t + T;
@@ -298,6 +309,14 @@ __global__ __launch_bounds__(kThreads) void panoptic_match_kernel(
         hit_p[sp] = 1;
         atomicAdd(tp + c, 1ull);
         atomicAdd(iou_sum + c, iou_fixed40((unsigned long long)inter, (unsigned long long)uni));
+        if (EXPORT) {
+          const int slot = atomicAdd(&s_matches, 1);
+          if (slot < T) {
+            int64_t* m = matches + ((long)blockIdx.x * T + slot) * 2;
+            m[0] = (int64_t)(keys_p[sp] - 1ull);
+            m[1] = (int64_t)(keys_t[st] - 1ull);
+          }
+        }
       }
     }
   }
@@ -307,6 +326,69 @@ __global__ __launch_bounds__(kThreads) void panoptic_match_kernel(
     if (ct >= 0 && ct != ignored && !hit_t[k]) atomicAdd(fn + ct, 1ull);
     if (cp >= 0 && cp != ignored && !hit_p[k] && !(2l * void_p[k] > (long)area_p[k]))
       atomicAdd(fp + cp, 1ull);
+  }
+  if (EXPORT && tid == 0) n_matches[blockIdx.x] = s_matches < T ? s_matches : T;
+}
+
+// ---- angular error -----------------------------------------------------------------------------
+// One thread per instance slot (identity mode: slot j against ground-truth id j) or per entry of a
+// match list (matched mode: predicted id % divisor against target id % divisor).  The angle of an
+// instance is atan2 of its two fixed-point sums in double; the error is rounded once to 2^-40 rad and
+// added as an integer, so the sum does not depend on the order.
+constexpr double kTwoPi = 6.283185307179586;
+constexpr double kAngleOne = 1099511627776.0;      // 2^40
+
+template <bool MATCHED>
+__global__ __launch_bounds__(kThreads) void angular_error_kernel(
+    const long long* __restrict__ vec, const int32_t* __restrict__ count,
+    const uint8_t* __restrict__ keep, int slots, const float* __restrict__ gt, int gt_slots,
+    const int64_t* __restrict__ matches, const int32_t* __restrict__ n_matches, int T, long divisor,
+    unsigned long long* __restrict__ acc, int32_t* __restrict__ flag) {
+  __shared__ unsigned long long s_err;
+  __shared__ unsigned int s_cnt;
+  const int tid = threadIdx.x;
+  if (tid == 0) { s_err = 0ull; s_cnt = 0u; }
+  __syncthreads();
+  const long img = blockIdx.y;
+  const int k = blockIdx.x * kThreads + tid;
+  long ps = -1, gs = -1;                       // predicted slot, ground-truth id
+  if (MATCHED) {
+    int nm = n_matches[img];
+    nm = nm < T ? nm : T;
+    if (k < nm) {
+      const int64_t* m = matches + (img * T + k) * 2;
+      const long pi = (long)(m[0] % divisor), gi = (long)(m[1] % divisor);
+      if (m[0] >= 0 && m[1] >= 0 && pi > 0 && gi > 0) { ps = pi; gs = gi; }   // (0: a stuff segment)
+    }
+  } else if (k >= 1 && k < slots) {
+    ps = k; gs = k;
+  }
+  if (ps > 0) {
+    const bool ps_ok = ps < slots;
+    if (!ps_ok) {
+      atomicOr(flag, 1);                       // (matched mode: a predicted instance beyond the sums)
+    } else if (count[img * slots + ps] > 0 && (!keep || keep[img * slots + ps])) {
+      if (gs >= gt_slots) {
+        atomicOr(flag, 1);
+      } else {
+        const float g = gt[img * gt_slots + gs];
+        if (g == g) {                          // NaN: this instance carries no orientation
+          const double s = (double)vec[(img * slots + ps) * 2];
+          const double c = (double)vec[(img * slots + ps) * 2 + 1];
+          double th = atan2(s, c);
+          if (th < 0.0) th += kTwoPi;
+          const double d = fmod(fabs(th - (double)g), kTwoPi);
+          const double err = fmin(d, kTwoPi - d);
+          atomicAdd(&s_err, (unsigned long long)llrint(err * kAngleOne));
+          atomicAdd(&s_cnt, 1u);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (tid == 0 && s_cnt) {
+    atomicAdd(acc, s_err);
+    atomicAdd(acc + 1, (unsigned long long)s_cnt);
   }
 }
 
@@ -380,10 +462,53 @@ extern "C" int emsa_panoptic_match(const void* workspace, int32_t n_images, int3
   if (n_images < 1 || max_segments < 1 || max_segments > kMaxSegments || num_categories < 1 ||
       max_instances_per_category < 1)
     return EMSA_E_SHAPE;
-  hipLaunchKernelGGL(panoptic_match_kernel, dim3(n_images), dim3(kThreads), 0, (hipStream_t)stream,
-                     (const unsigned char*)workspace, max_segments, num_categories, ignored_label,
-                     (long)max_instances_per_category, (unsigned long long*)tp,
-                     (unsigned long long*)fn, (unsigned long long*)fp,
-                     (unsigned long long*)iou_sum, flags);
+  hipLaunchKernelGGL(panoptic_match_kernel<false>, dim3(n_images), dim3(kThreads), 0,
+                     (hipStream_t)stream, (const unsigned char*)workspace, max_segments,
+                     num_categories, ignored_label, (long)max_instances_per_category,
+                     (unsigned long long*)tp, (unsigned long long*)fn, (unsigned long long*)fp,
+                     (unsigned long long*)iou_sum, flags, (int64_t*)nullptr, (int32_t*)nullptr);
+  return emsa_launch_status();
+}
+
+extern "C" int emsa_panoptic_match_pairs(const void* workspace, int32_t n_images,
+                                         int32_t max_segments, int32_t num_categories,
+                                         int32_t ignored_label, int64_t max_instances_per_category,
+                                         int64_t* tp, int64_t* fn, int64_t* fp, int64_t* iou_sum,
+                                         int64_t* matches, int32_t* n_matches, int32_t* flags,
+                                         void* stream) {
+  if (!workspace || !tp || !fn || !fp || !iou_sum || !matches || !n_matches || !flags)
+    return EMSA_E_ARG;
+  if (n_images < 1 || max_segments < 1 || max_segments > kMaxSegments || num_categories < 1 ||
+      max_instances_per_category < 1)
+    return EMSA_E_SHAPE;
+  hipLaunchKernelGGL(panoptic_match_kernel<true>, dim3(n_images), dim3(kThreads), 0,
+                     (hipStream_t)stream, (const unsigned char*)workspace, max_segments,
+                     num_categories, ignored_label, (long)max_instances_per_category,
+                     (unsigned long long*)tp, (unsigned long long*)fn, (unsigned long long*)fp,
+                     (unsigned long long*)iou_sum, flags, matches, n_matches);
+  return emsa_launch_status();
+}
+
+extern "C" int emsa_angular_error(const int64_t* vec_sum, const int32_t* count, const uint8_t* keep,
+                                  int32_t n, int32_t slots, const float* gt_angles,
+                                  int32_t gt_slots, const int64_t* matches,
+                                  const int32_t* n_matches, int32_t max_segments,
+                                  int64_t label_divisor, int64_t* acc, int32_t* flag, void* stream) {
+  if (!vec_sum || !count || !gt_angles || !acc || !flag) return EMSA_E_ARG;
+  if ((matches == nullptr) != (n_matches == nullptr)) return EMSA_E_ARG;
+  if (n < 1 || n > 65535 || slots < 2 || gt_slots < 2) return EMSA_E_SHAPE;
+  hipStream_t st = (hipStream_t)stream;
+  if (matches) {
+    if (max_segments < 1 || max_segments > kMaxSegments || label_divisor < 1) return EMSA_E_SHAPE;
+    hipLaunchKernelGGL(angular_error_kernel<true>, dim3((max_segments + kThreads - 1) / kThreads, n),
+                       dim3(kThreads), 0, st, (const long long*)vec_sum, count, keep, slots,
+                       gt_angles, gt_slots, matches, n_matches, max_segments, (long)label_divisor,
+                       (unsigned long long*)acc, flag);
+  } else {
+    hipLaunchKernelGGL(angular_error_kernel<false>, dim3((slots + kThreads - 1) / kThreads, n),
+                       dim3(kThreads), 0, st, (const long long*)vec_sum, count, keep, slots,
+                       gt_angles, gt_slots, (const int64_t*)nullptr, (const int32_t*)nullptr, 0, 1l,
+                       (unsigned long long*)acc, flag);
+  }
   return emsa_launch_status();
 }

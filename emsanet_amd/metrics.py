@@ -2,7 +2,9 @@
 """
 Validation metrics on device: mean IoU and panoptic quality, the two values the reference keeps its
 checkpoints by (`valid_semantic_miou`, `valid_panoptic_all_deeplab_pq`: /root/reference/main.py:229,
-emsanet/args.py:1054).
+emsanet/args.py:1054), and the other checkpoint keys of the reference's evaluation commands: scene
+accuracy (`bacc`) and the mean absolute angular error of the orientations (`mae_gt_deg`,
+`panoptic_mae_deeplab_deg`).  `emsanet_amd.evaluation.ValidationEvaluator` composes them.
 
 The reference takes them from `metric.MeanIntersectionOverUnion` / `metric.PanopticQuality` of the
 un-vendored `nicr_mt_scene_analysis` library.  The classes here keep that surface
@@ -12,6 +14,8 @@ kernels on the current stream (no device-to-host copy, no synchronisation, no al
 first call for a shape, so it can be captured into a graph); the one host read is in `compute()`.
 Arithmetic: csrc/metrics.hip -- integer sums only, so results are independent of the execution order.
 """
+import math
+
 import torch
 
 from . import _lib
@@ -130,11 +134,13 @@ class PanopticQuality:
             raise ValueError(f"PanopticQuality: max_segments={max_segments} outside [1, 1024]")
         self._state = None                      # int64 [4*K + 1]: tp, fn, fp, iou_sum, then 2 int32 flags
         self._ws = {}                           # (device, images) -> workspace
+        self._matches = {}                      # images -> (matches, n_matches)
 
     def _buffers(self, device, n):
         if self._state is None or self._state.device != device:
             self._state = torch.zeros(4 * self.num_categories + 1, device=device, dtype=torch.int64)
             self._ws = {}
+            self._matches = {}
         ws = self._ws.get(n)
         if ws is None:
             nbytes = _lib.lib().emsa_panoptic_workspace_bytes(n, self.max_segments)
@@ -142,6 +148,17 @@ class PanopticQuality:
         return self._state, ws
 
     def update(self, preds, targets):
+        self._update(preds, targets, False)
+
+    def update_with_matches(self, preds, targets):
+        """`update(preds, targets)` through `emsa_panoptic_match_pairs`: the same counts, and
+        -> (matches (N, max_segments, 2) int64, n_matches (N,) int32) on the device: the first
+        n_matches[i] rows of matches[i] are the (predicted id, target id) pairs of image i that matched,
+        in no particular order; the rows behind them are stale.  Both tensors belong to this object and
+        are overwritten by its next `update_with_matches` of the same batch size."""
+        return self._update(preds, targets, True)
+
+    def _update(self, preds, targets, export):
         for what, t in (('preds', preds), ('targets', targets)):
             if not torch.is_tensor(t):
                 raise TypeError(f"PanopticQuality.update: {what} must be a tensor")
@@ -162,10 +179,23 @@ class PanopticQuality:
         L = _lib.lib()
         check(L.emsa_panoptic_pairs(p.data_ptr(), t.data_ptr(), n, hw, self.max_segments, ws.data_ptr(),
                                     flags, _stream()), 'emsa_panoptic_pairs')
+        if export:
+            m = self._matches.get(n)
+            if m is None:
+                m = self._matches[n] = (
+                    torch.zeros((n, self.max_segments, 2), device=p.device, dtype=torch.int64),
+                    torch.zeros(n, device=p.device, dtype=torch.int32))
+            check(L.emsa_panoptic_match_pairs(ws.data_ptr(), n, self.max_segments, k, self.ignored_label,
+                                              self.max_instances_per_category, base, base + 8 * k,
+                                              base + 16 * k, base + 24 * k, m[0].data_ptr(),
+                                              m[1].data_ptr(), flags, _stream()),
+                  'emsa_panoptic_match_pairs')
+            return m
         check(L.emsa_panoptic_match(ws.data_ptr(), n, self.max_segments, k, self.ignored_label,
                                     self.max_instances_per_category, base, base + 8 * k,
                                     base + 16 * k, base + 24 * k, flags, _stream()),
               'emsa_panoptic_match')
+        return None
 
     def reset(self):
         if self._state is not None:
@@ -204,6 +234,171 @@ class PanopticQuality:
             for j, key in enumerate(('pq', 'sq', 'rq')):
                 out[f'{g}_{key}'] = sum(r[j] for r in rows) / len(rows) if rows else 0.0
         return out
+
+
+class SceneAccuracy:
+    """`valid_scene_acc` / `valid_scene_bacc` from the confusion matrix cm[target][pred] of (N,) scene
+    labels (`emsa_confusion_matrix`; row and column 0 = void dropped when `ignore_first_class`).
+    acc = trace / total of the kept matrix; bacc = mean of cm[c][c] / row_c over the classes that occur
+    in the targets (row_c > 0) -- [U]: the library's balanced accuracy is not vendored; averaging
+    the recall over the classes present in the targets is the usual definition.  0.0 without any
+    counted sample.  A label outside [0, n_classes_with_void) is not counted and makes `compute()`
+    raise."""
+
+    def __init__(self, n_classes_with_void, ignore_first_class=True):
+        self._cm = MeanIntersectionOverUnion(n_classes_with_void, ignore_first_class)
+        self.n_classes = self._cm.n_classes
+        self.ignore_first_class = self._cm.ignore_first_class
+
+    def update(self, pred_idx_with_void, target):
+        for what, x in (('pred_idx_with_void', pred_idx_with_void), ('target', target)):
+            if not torch.is_tensor(x):
+                raise TypeError(f"SceneAccuracy.update: {what} must be a tensor")
+            if x.dtype not in _LABEL_DTYPES:
+                raise TypeError(f"SceneAccuracy.update: {what} has dtype {x.dtype}; int64, int32 or uint8 "
+                                "labels only")
+        if pred_idx_with_void.dim() != 1 or pred_idx_with_void.shape != target.shape:
+            raise ValueError(f"SceneAccuracy.update: pred {tuple(pred_idx_with_void.shape)} vs target "
+                             f"{tuple(target.shape)}; (N,) labels of equal shape")
+        p = _label_map(pred_idx_with_void, 'SceneAccuracy.update', 'pred_idx_with_void')
+        t = _label_map(target, 'SceneAccuracy.update', 'target')
+        self._cm.update(p, t)
+
+    @property
+    def confusion_matrix(self):
+        return self._cm.confusion_matrix
+
+    def reset(self):
+        self._cm.reset()
+
+    def compute(self):
+        if self._cm._state is None:
+            return {'acc': 0.0, 'bacc': 0.0}
+        s = self._cm._state.cpu()
+        if int(s[-1]) != 0:
+            raise ValueError(f"SceneAccuracy: n_invalid = {int(s[-1])} samples carried a label outside "
+                             f"[0, {self.n_classes}) and were not counted")
+        cm = s[:-1].view(self.n_classes, self.n_classes)
+        if self.ignore_first_class:
+            cm = cm[1:, 1:]
+        total, rows, tp = int(cm.sum()), cm.sum(1), cm.diagonal()
+        present = rows > 0
+        if total == 0:
+            return {'acc': 0.0, 'bacc': 0.0}
+        return {'acc': int(tp.sum()) / total,
+                'bacc': float((tp[present].double() / rows[present].double()).mean())}
+
+
+ANGLE_ONE = 1 << 40                                                    # fixed point of the error sum
+
+
+def _angle_inputs(name, vec, count, gt_table, keep):
+    for what, t, dtypes in (('vec', vec, (torch.int64,)), ('count', count, (torch.int32,)),
+                            ('gt_table', gt_table, (torch.float32,)),
+                            ('keep', keep, (torch.uint8, torch.bool))):
+        if t is None and what == 'keep':
+            continue
+        if not torch.is_tensor(t):
+            raise TypeError(f"{name}: {what} must be a tensor")
+        if t.dtype not in dtypes:
+            raise TypeError(f"{name}: {what} has dtype {t.dtype}; expected {' or '.join(map(str, dtypes))}")
+    if vec.dim() != 3 or vec.shape[2] != 2 or tuple(count.shape) != tuple(vec.shape[:2]) or \
+            gt_table.dim() != 2 or gt_table.shape[0] != vec.shape[0] or \
+            (keep is not None and keep.shape != count.shape):
+        raise ValueError(f"{name}: vec {tuple(vec.shape)}, count {tuple(count.shape)}, gt_table "
+                         f"{tuple(gt_table.shape)}, keep {None if keep is None else tuple(keep.shape)}; "
+                         "expected (N, slots, 2), (N, slots), (N, gt_slots), (N, slots)")
+    if vec.shape[1] < 2 or gt_table.shape[1] < 2:
+        raise ValueError(f"{name}: at least 2 slots on either side (slot 0 is 'no instance')")
+    for what, t in (('vec', vec), ('count', count), ('gt_table', gt_table), ('keep', keep)):
+        if t is not None and not t.is_cuda:
+            raise NotImplementedError(f"{name}: {what} is a CPU tensor; the metrics count on the GPU only")
+        if t is not None and t.device != vec.device:
+            raise ValueError(f"{name}: {what} on {t.device}, vec on {vec.device}")
+    k = None if keep is None else keep.contiguous()
+    if k is not None and k.dtype == torch.bool:
+        k = k.view(torch.uint8)
+    return vec.contiguous(), count.contiguous(), gt_table.contiguous(), k
+
+
+class MeanAbsoluteAngularError:
+    """`valid_orientation_mae_gt_*` / `valid_panoptic_mae_deeplab_*`: the mean over the compared
+    instances of the absolute angular difference (in [0, pi]) between the instance's mean predicted
+    orientation and its ground-truth angle (`emsa_angular_error`).
+
+    vec (N, slots, 2) int64 / count (N, slots) int32: the per-instance sums of
+    `postprocessing.instance_orientation_sums`; gt_table (N, gt_slots) float32: the angle in rad per
+    ground-truth instance id, NaN = none (`targets.orientation_table`); keep (N, slots) uint8 / bool or
+    None.  `update` compares slot j with ground-truth id j; `update_matched` compares, for every pair of
+    `PanopticQuality.update_with_matches`, predicted slot pred_id % label_divisor with ground-truth id
+    target_id % label_divisor (stuff pairs skipped).  An instance without pixels, with keep 0 or with a
+    NaN ground truth is skipped.  Which instances the library compares and that it averages over
+    instances rather than pixels is [U] (the library is not vendored).
+
+    `compute()` -> {'mae_rad', 'mae_deg'}: NaN, not 0.0, when nothing was compared -- the value is ranked
+    "lower is better", and a 0.0 would be kept as the best ever.  It is the one host read and raises
+    ValueError when an id lay outside the tables (such an instance is not compared)."""
+
+    def __init__(self):
+        self._state = None                      # int64 [3]: error sum (2^-40 rad), count, int32 flag
+
+    def _buffers(self, device):
+        if self._state is None or self._state.device != device:
+            self._state = torch.zeros(3, device=device, dtype=torch.int64)
+        return self._state
+
+    def _launch(self, name, vec, count, gt_table, keep, matches, n_matches, max_segments, divisor):
+        v, c, g, k = _angle_inputs(name, vec, count, gt_table, keep)
+        s = self._buffers(v.device)
+        check(_lib.lib().emsa_angular_error(
+            v.data_ptr(), c.data_ptr(), None if k is None else k.data_ptr(), v.shape[0], v.shape[1],
+            g.data_ptr(), g.shape[1], None if matches is None else matches.data_ptr(),
+            None if n_matches is None else n_matches.data_ptr(), max_segments, divisor, s.data_ptr(),
+            s.data_ptr() + 16, _stream()), 'emsa_angular_error')
+
+    def update(self, vec, count, gt_table, keep=None):
+        self._launch('MeanAbsoluteAngularError.update', vec, count, gt_table, keep, None, None, 0, 1)
+
+    def update_matched(self, vec, count, gt_table, matches, n_matches, label_divisor, keep=None):
+        name = 'MeanAbsoluteAngularError.update_matched'
+        for what, t, dtype in (('matches', matches, torch.int64), ('n_matches', n_matches, torch.int32)):
+            if not torch.is_tensor(t):
+                raise TypeError(f"{name}: {what} must be a tensor")
+            if t.dtype != dtype:
+                raise TypeError(f"{name}: {what} has dtype {t.dtype}; expected {dtype}")
+        if matches.dim() != 3 or matches.shape[2] != 2 or tuple(n_matches.shape) != (matches.shape[0],) or \
+                not torch.is_tensor(vec) or matches.shape[0] != vec.shape[0] or int(label_divisor) < 1:
+            raise ValueError(f"{name}: matches {tuple(matches.shape)}, n_matches {tuple(n_matches.shape)}; "
+                             "expected (N, max_segments, 2) and (N,) for the N images of vec, and a "
+                             "positive label_divisor")
+        if not matches.is_contiguous() or not n_matches.is_contiguous():
+            raise ValueError(f"{name}: matches / n_matches must be contiguous")
+        if not matches.is_cuda or not n_matches.is_cuda:
+            raise NotImplementedError(f"{name}: matches is a CPU tensor; the metrics count on the GPU only")
+        self._launch(name, vec, count, gt_table, keep, matches, n_matches, matches.shape[1],
+                     int(label_divisor))
+
+    def reset(self):
+        if self._state is not None:
+            self._state.zero_()
+
+    def counts(self):
+        """host copy of the state -> (error sum in units of 2^-40 rad, compared instances); raises like
+        `compute()`"""
+        if self._state is None:
+            return 0, 0
+        s = self._state.cpu()
+        if int(s[2:].view(torch.int32)[0]):
+            raise ValueError("MeanAbsoluteAngularError: an instance id lay outside the orientation tables "
+                             "(ground-truth id >= gt_slots, or predicted instance >= slots)")
+        return int(s[0]), int(s[1])
+
+    def compute(self):
+        total, n = self.counts()
+        if n == 0:
+            return {'mae_rad': float('nan'), 'mae_deg': float('nan')}
+        rad = total / ANGLE_ONE / n
+        return {'mae_rad': rad, 'mae_deg': math.degrees(rad)}
 
 
 def panoptic_targets(semantic, instance, is_thing, label_divisor):

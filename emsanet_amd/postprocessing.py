@@ -423,6 +423,8 @@ class PanopticPostprocessing:
             cls = m['instance_class']
             keep = table[cls.clamp(min=0).long()].bool() & (cls >= 0)
             r['orientations_panoptic_segmentation_deeplab_instance'] = orientation_dicts(vec, cnt, keep)
+            # the keep table itself, (N, top_k + 1) bool: evaluation.ValidationEvaluator reads it
+            r['orientations_panoptic_segmentation_deeplab_instance_keep'] = keep
         return r
 
 

@@ -545,6 +545,25 @@ int emsa_normalize_depth(const uint16_t* depth, float* out, int64_t total, float
  *                           prediction: fp[cat] += 1 unless 2*void_p > area_p.  tp / fn / fp /
  *                           iou_sum int64[num_categories]; a category >= num_categories sets
  *                           flags[1] and the segment is skipped.  flags int32[2] (DEVICE).
+ *   emsa_panoptic_match_pairs  the same matching with the same additions to tp / fn / fp / iou_sum,
+ *                           which also writes the matched segments of every image as (predicted id,
+ *                           target id) into matches int64[n_images][max_segments][2] and their
+ *                           number into n_matches int32[n_images] (both overwritten, not added to).
+ *                           The order inside an image's list is unspecified (slots are claimed first
+ *                           come first); entries beyond n_matches are not written.
+ *   emsa_angular_error      mean-absolute-angular-error sums.  vec_sum int64[n][slots][2] / count
+ *                           int32[n][slots] from emsa_instance_orientation, keep uint8[n][slots] or
+ *                           NULL, gt_angles float[n][gt_slots] in rad (NaN = the instance carries no
+ *                           orientation).  matches == NULL (then n_matches == NULL too): slot j is
+ *                           compared with ground-truth id j.  Otherwise every entry of the match
+ *                           lists of emsa_panoptic_match_pairs compares predicted slot pred_id %
+ *                           label_divisor with ground-truth id target_id % label_divisor; a pair
+ *                           with an instance part of 0 (a stuff segment) is skipped.  Per compared
+ *                           instance, in double: a = atan2(sum_sin, sum_cos) mod 2 pi (0 for a zero
+ *                           sum), d = |a - gt| mod 2 pi, err = min(d, 2 pi - d); acc[0] +=
+ *                           round(err * 2^40), acc[1] += 1 (acc int64[2]).  Skipped: count 0, keep
+ *                           0, gt NaN, and a ground-truth id >= gt_slots or a predicted slot >=
+ *                           slots of an otherwise compared instance, which also set *flag (int32).
  * ------------------------------------------------------------------------------------------ */
 #define EMSA_LABEL_I64 0
 #define EMSA_LABEL_I32 1
@@ -562,6 +581,15 @@ int emsa_panoptic_match(const void* workspace, int32_t n_images, int32_t max_seg
                         int32_t num_categories, int32_t ignored_label,
                         int64_t max_instances_per_category, int64_t* tp, int64_t* fn, int64_t* fp,
                         int64_t* iou_sum, int32_t* flags, void* stream);
+int emsa_panoptic_match_pairs(const void* workspace, int32_t n_images, int32_t max_segments,
+                              int32_t num_categories, int32_t ignored_label,
+                              int64_t max_instances_per_category, int64_t* tp, int64_t* fn,
+                              int64_t* fp, int64_t* iou_sum, int64_t* matches, int32_t* n_matches,
+                              int32_t* flags, void* stream);
+int emsa_angular_error(const int64_t* vec_sum, const int32_t* count, const uint8_t* keep, int32_t n,
+                       int32_t slots, const float* gt_angles, int32_t gt_slots,
+                       const int64_t* matches, const int32_t* n_matches, int32_t max_segments,
+                       int64_t label_divisor, int64_t* acc, int32_t* flag, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Training targets (csrc/targets.hip): the per-scale targets of emsanet_amd.loss.TrainingLosses from
