@@ -22,9 +22,36 @@ from . import functional as Fn
 from ._lib import check
 
 
+def _dev(t, name):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise _lib.EmsaError(f"{name}: expected a tensor on the GPU")
+    return t
+
+
+def _f32(t, name):
+    """the kernels read `float*`: fp32 passes through untouched, bf16 / fp16 / fp64 are converted,
+    anything else is refused (never reinterpreted)"""
+    if _dev(t, name).dtype == torch.float32:
+        return t
+    if not t.dtype.is_floating_point:
+        raise _lib.EmsaError(f"{name}: expected a floating-point tensor, got {t.dtype}")
+    return t.float()
+
+
+def _int(t, name, dtype):
+    """the kernels read `int32_t*` / `int64_t*`: the other integer widths are converted"""
+    if _dev(t, name).dtype == dtype:
+        return t.contiguous()
+    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise _lib.EmsaError(f"{name}: expected an integer tensor, got {t.dtype}")
+    return t.to(dtype).contiguous()
+
+
 def softmax_argmax(logits):
     """logits (N,C,H,W) or (N,C) -> (score, idx): idx = argmax over C (int64), score = its
-    softmax probability (== torch.softmax(logits, 1).max(1))"""
+    softmax probability (== torch.softmax(logits, 1).max(1)); 16-bit logits are read as their
+    fp32 images"""
+    logits = _f32(logits, 'softmax_argmax: logits')
     if logits.dim() == 2:
         n, c = logits.shape
         cp = Fn.pad4(c)
@@ -51,8 +78,8 @@ def softmax_argmax(logits):
     return score, idx
 
 
-def _u8(m):
-    return None if m is None else m.reshape(-1).to(torch.uint8).contiguous()
+def _u8(m, name='mask'):
+    return None if m is None else _dev(m, name).reshape(-1).to(torch.uint8).contiguous()
 
 
 def instance_centers(heatmap, threshold=0.1, nms_kernel_size=17, top_k=64, foreground=None,
@@ -61,7 +88,7 @@ def instance_centers(heatmap, threshold=0.1, nms_kernel_size=17, top_k=64, foreg
     n_centers (N,) int32 (defaults: /root/reference/emsanet/args.py:469-504).  The top-k is exact
     over ALL pixels that survive the NMS (ref decoder.py:95-104), also on saturated plateaus with
     tens of thousands of survivors; return_survivors: also that count per image (N,) int32"""
-    x = Fn.as_act(heatmap)
+    x = Fn.as_act(_f32(heatmap, 'instance_centers: heatmap'))
     n, _, h, w = x.shape
     L = _lib.lib()
     cap = L.emsa_center_ws_entries(h, w, top_k)
@@ -75,7 +102,7 @@ def instance_centers(heatmap, threshold=0.1, nms_kernel_size=17, top_k=64, foreg
     centers = Fn._empty((n, top_k, 2), dev)
     scores = Fn._empty((n, top_k), dev)
     n_centers = torch.empty(n, device=dev, dtype=torch.int32)
-    fg = _u8(foreground)
+    fg = _u8(foreground, 'instance_centers: foreground')
     check(L.emsa_instance_centers(Fn._p(x), Fn.ld_of(x), n, h, w, nms_kernel_size, threshold,
                                   top_k, Fn._p(fg), ws_count.data_ptr(), Fn._p(ws_score),
                                   ws_pos.data_ptr(), Fn._p(centers), Fn._p(scores),
@@ -89,11 +116,16 @@ def instance_assign(offsets, centers, n_centers, foreground=None, normalized_off
                     offset_distance_threshold=None):
     """offsets (N,2,H,W) (dy, dx; in units of the image height / width when normalized) ->
     instance ids (N,H,W) int32: 1 + index of the nearest centre, 0 = no instance"""
-    o = Fn.as_act(offsets)
+    o = Fn.as_act(_f32(offsets, 'instance_assign: offsets'))
     n, _, h, w = o.shape
+    centers = _f32(centers, 'instance_assign: centers').contiguous()
+    n_centers = _int(n_centers, 'instance_assign: n_centers', torch.int32)
+    if centers.dim() != 3 or centers.shape[0] != n or centers.shape[2] != 2 or n_centers.numel() != n:
+        raise _lib.EmsaError(f"instance_assign: centers {tuple(centers.shape)} / n_centers "
+                             f"{tuple(n_centers.shape)} do not describe {n} images")
     ids = torch.empty((n, h, w), device=o.device, dtype=torch.int32)
     sy, sx = (float(h), float(w)) if normalized_offset else (1.0, 1.0)
-    fg = _u8(foreground)
+    fg = _u8(foreground, 'instance_assign: foreground')
     check(_lib.lib().emsa_instance_assign(Fn._p(o), Fn.ld_of(o), n, h, w, sy, sx, Fn._p(centers),
                                           n_centers.data_ptr(), centers.shape[1], Fn._p(fg),
                                           float(offset_distance_threshold or 0.0),
@@ -185,8 +217,8 @@ def panoptic_merge(semantic_idx, instance_ids, classes_is_thing, top_k=64, label
     dev = semantic_idx.device
     nc = len(classes_is_thing)
     thing = thing_table(classes_is_thing, dev)
-    sem = semantic_idx.contiguous()
-    ids = instance_ids.contiguous()
+    sem = _int(semantic_idx, 'panoptic_merge: semantic_idx', torch.int64)
+    ids = _int(instance_ids, 'panoptic_merge: instance_ids', torch.int32)
     ws_votes = torch.empty(n * (top_k + 1) * nc, device=dev, dtype=torch.int32)
     ws_class = torch.empty(n * (top_k + 1), device=dev, dtype=torch.int32)
     pan_sem = torch.empty((n, h, w), device=dev, dtype=torch.int64)
@@ -206,11 +238,12 @@ def instance_stats(ids, slots, value=None, mask=None):
     per-instance pixel count (and fixed-point score sum) by integer atomics (order-independent)"""
     n, h, w = ids.shape
     dev = ids.device
-    ids = ids.contiguous()
+    ids = _int(ids, 'instance_stats: ids', torch.int32)
     area = torch.empty((n, slots), device=dev, dtype=torch.int32)
     ssum = torch.empty((n, slots), device=dev, dtype=torch.int64) if value is not None else None
-    v = None if value is None else value.contiguous()
-    check(_lib.lib().emsa_instance_stats(ids.data_ptr(), Fn._p(v), Fn._p(_u8(mask)), n, h * w, slots,
+    v = None if value is None else _f32(value, 'instance_stats: value').contiguous()
+    mask = _u8(mask, 'instance_stats: mask')
+    check(_lib.lib().emsa_instance_stats(ids.data_ptr(), Fn._p(v), Fn._p(mask), n, h * w, slots,
                                          Fn._p(ssum), area.data_ptr(), Fn._stream()),
           'emsa_instance_stats')
     return (area, ssum) if value is not None else area
@@ -229,12 +262,16 @@ def panoptic_scores(semantic_score, pan_instance, pan_semantic, center_scores):
     dev = pan_instance.device
     top_k = center_scores.shape[1]
     slots = top_k + 1
+    semantic_score = _f32(semantic_score, 'panoptic_scores: semantic_score').contiguous()
+    center_scores = _f32(center_scores, 'panoptic_scores: center_scores').contiguous()
+    pan_instance = _int(pan_instance, 'panoptic_scores: pan_instance', torch.int32)
+    pan_semantic = _int(pan_semantic, 'panoptic_scores: pan_semantic', torch.int64)
     ws_sum = torch.empty((n, slots), device=dev, dtype=torch.int64)
     area = torch.empty((n, slots), device=dev, dtype=torch.int32)
     inst_sem = Fn._empty((n, slots), dev)
     inst_pan = Fn._empty((n, slots), dev)
     o = [Fn._empty((n, h, w), dev) for _ in range(3)]
-    check(_lib.lib().emsa_panoptic_scores(Fn._p(semantic_score.contiguous()), pan_instance.data_ptr(),
+    check(_lib.lib().emsa_panoptic_scores(Fn._p(semantic_score), pan_instance.data_ptr(),
                                           pan_semantic.data_ptr(), Fn._p(center_scores), n, h * w,
                                           top_k, ws_sum.data_ptr(), area.data_ptr(), Fn._p(inst_sem),
                                           Fn._p(inst_pan), Fn._p(o[0]), Fn._p(o[1]), Fn._p(o[2]),
@@ -246,13 +283,14 @@ def panoptic_scores(semantic_score, pan_instance, pan_semantic, center_scores):
 def instance_orientation_sums(orientation, ids, slots, mask=None):
     """orientation (N,2,H,W) (channels: sin, cos -- [U], like oracle/instance_loss_oracle.Spec), ids
     (N,H,W) int32 -> (vec (N,slots,2) int64 fixed-point sums, count (N,slots) int32)"""
-    o = Fn.as_act(orientation.float() if orientation.dtype != torch.float32 else orientation)
+    o = Fn.as_act(_f32(orientation, 'instance_orientation_sums: orientation'))
     n, _, h, w = o.shape
     dev = o.device
-    ids = ids.contiguous()
+    ids = _int(ids, 'instance_orientation_sums: ids', torch.int32)
+    mask = _u8(mask, 'instance_orientation_sums: mask')
     vec = torch.empty((n, slots, 2), device=dev, dtype=torch.int64)
     cnt = torch.empty((n, slots), device=dev, dtype=torch.int32)
-    check(_lib.lib().emsa_instance_orientation(Fn._p(o), Fn.ld_of(o), ids.data_ptr(), Fn._p(_u8(mask)),
+    check(_lib.lib().emsa_instance_orientation(Fn._p(o), Fn.ld_of(o), ids.data_ptr(), Fn._p(mask),
                                                n, h * w, slots, vec.data_ptr(), cnt.data_ptr(),
                                                Fn._stream()), 'emsa_instance_orientation')
     return vec, cnt

@@ -37,6 +37,10 @@ def fake_lib(monkeypatch):
     fake = _FakeLib()
     monkeypatch.setattr(_lib, '_lib', fake)
     monkeypatch.setattr(functional, '_stream', lambda: 0)
+    # like _bypass_device_check: the post-processing wrappers refuse host tensors, the dry run feeds
+    # host tensors to the stubbed library
+    from emsanet_amd import postprocessing
+    monkeypatch.setattr(postprocessing, '_dev', lambda t, name: t)
     return fake
 
 

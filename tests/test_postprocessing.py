@@ -41,6 +41,7 @@ def _heatmap(n, h, w, seed, n_blobs=12):
 
 @pytest.mark.parametrize('top_k,with_fg', [(64, False), (5, False), (64, True)])
 def test_instance_centers_and_assignment(top_k, with_fg):
+    import postprocessing_cases as C
     from emsanet_amd.postprocessing import instance_assign, instance_centers
     from oracle import postprocessing_oracle as O
     n, h, w = 2, 60, 80
@@ -60,11 +61,15 @@ def test_instance_centers_and_assignment(top_k, with_fg):
     ids = instance_assign(off.to(DEV), centers, nc, fg.to(DEV) if with_fg else None, True)
     rid = O.instance_assign(off, ref, fg, True)
     mism = (ids.cpu() != rid).float().mean().item()
-    assert mism <= 1e-4, mism                      # exact up to fp ties between two centres
+    assert mism <= 1e-4, mism                      # exact up to fp ties between two centres ...
+    # ... and every pixel that differs from the fp64 arg-min IS such a tie, within the fp32 rounding
+    # bound of the kernel's expression (tests/postprocessing_cases.py: assign_bound)
+    C.assign_check(ids.cpu(), off, centers.cpu(), nc.cpu(), fg, True, None, 1e-4)
     # distance threshold and the no-centre image
     ids2 = instance_assign(off.to(DEV), centers, nc, None, True, offset_distance_threshold=6)
     rid2 = O.instance_assign(off, ref, None, True, max_distance=6)
     assert (ids2.cpu() != rid2).float().mean().item() <= 1e-3
+    C.assign_check(ids2.cpu(), off, centers.cpu(), nc.cpu(), None, True, 6.0, 1e-3)
     c0, s0, n0 = instance_centers(torch.zeros(1, 1, 20, 20, device=DEV))
     assert int(n0[0]) == 0
     assert int(instance_assign(off[:1, :, :20, :20].contiguous().to(DEV), c0, n0).abs().max()) == 0
