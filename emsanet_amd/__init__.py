@@ -25,4 +25,7 @@ def __getattr__(name):
     if name == 'TrainingAugmenter':
         from .augment import TrainingAugmenter
         return TrainingAugmenter
+    if name in ('InferenceOutputPacker', 'write_mapping_output'):
+        from . import export
+        return getattr(export, name)
     raise AttributeError(name)

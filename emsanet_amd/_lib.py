@@ -50,6 +50,14 @@ class EmsaTargetScale(Structure):
                 ('orientation_foreground', c_void_p)]
 
 
+class EmsaExportJob(Structure):
+    _fields_ = [('src0', c_void_p), ('src1', c_void_p), ('depth', c_void_p), ('lut', c_void_p),
+                ('dst', c_void_p), ('divisor', c_int64), ('max_depth', ctypes.c_double),
+                ('kind', c_int32), ('src0_dtype', c_int32), ('src1_dtype', c_int32),
+                ('depth_dtype', c_int32), ('lut_size', c_int32), ('add', c_int32), ('h', c_int32),
+                ('w', c_int32)]
+
+
 _P = c_void_p          # device pointers travel as integers (tensor.data_ptr())
 _GP = POINTER(EmsaConvGeom)
 _TP = POINTER(EmsaTargetScale)
@@ -169,6 +177,11 @@ SIGNATURES = {
                                           _P, _P, _P, _P, _P]),
     'emsa_angular_error': (c_int, [_P, _P, _P, c_int32, c_int32, _P, c_int32, _P, _P, c_int32, c_int64,
                                    _P, _P, _P]),
+    'emsa_export_pack': (c_int, [POINTER(EmsaExportJob), c_int32, c_int32, c_int32, c_int32, _P, _P]),
+    'emsa_export_instance_ranks': (c_int, [_P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P,
+                                           _P, _P]),
+    'emsa_export_instance_masks': (c_int, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                           _P, c_int32, _P, _P, c_int32, _P, _P]),
     'emsa_targets_workspace_bytes': (c_int64, [c_int32, c_int32, c_int32]),
     'emsa_targets_table_entries': (c_int, [c_int32]),
     'emsa_targets_stats': (c_int, [_P, c_int32, _P, c_int32, _P, c_int32, c_int32, c_int32, c_int32, _TP,

@@ -72,13 +72,20 @@ def _repair_and_instantiate(graph, kept):
 
 
 class GraphedInference:
-    """model must be in eval mode; inputs must keep shape/dtype/device of `example_batch`."""
+    """model must be in eval mode; inputs must keep shape/dtype/device of `example_batch`.
+    after: optional callable(prediction, batch) that only launches kernels on the current stream (for
+    instance `export.InferenceOutputPacker.pack`): it runs behind the forward in the warm-up runs and in
+    the capture, its result is `static_after` and is rewritten by every replay.  It is called `warmup`
+    times before the capture and must allocate nothing in the captured call (a packer with `ring` buffer
+    sets needs ring <= warmup + 1)."""
 
-    def __init__(self, model, example_batch, do_postprocessing=False, warmup=3):
+    def __init__(self, model, example_batch, do_postprocessing=False, warmup=3, after=None):
         if model.training:
             raise ValueError("GraphedInference captures the eval-mode forward")
         self.model = model
         self.do_postprocessing = do_postprocessing
+        self.after = after
+        self.static_after = None
         self.warmup = warmup
         self.static_in = {k: v.clone() for k, v in example_batch.items() if torch.is_tensor(v)}
         self.extra = {k: v for k, v in example_batch.items() if not torch.is_tensor(v)}
@@ -100,12 +107,16 @@ class GraphedInference:
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side), torch.no_grad():
             for _ in range(self.warmup):  # packs weights, sets kernel attributes, warms the pool
-                model({**self.static_in, **self.extra}, do_postprocessing=self.do_postprocessing)
+                out = model({**self.static_in, **self.extra}, do_postprocessing=self.do_postprocessing)
+                if self.after is not None:
+                    self.after(out, {**self.static_in, **self.extra})
         torch.cuda.current_stream().wait_stream(side)
         self.graph, kept = _new_graph()
         with torch.no_grad(), torch.cuda.graph(self.graph, capture_error_mode=_CAPTURE_MODE):
             self.static_out = model({**self.static_in, **self.extra},
                                     do_postprocessing=self.do_postprocessing)
+            if self.after is not None:
+                self.static_after = self.after(self.static_out, {**self.static_in, **self.extra})
         self.graph_info = _repair_and_instantiate(self.graph, kept)
         self._key = self._weights_key()
         self.captures += 1

@@ -448,11 +448,15 @@ class PanopticPostprocessing:
             r['panoptic_segmentation_deeplab_panoptic_score'] = sc['panoptic_score']
         else:
             area = instance_stats(m['instance'], self.inst.top_k + 1)
-        r['panoptic_segmentation_deeplab_instance_meta'] = instance_meta(
+        meta = r['panoptic_segmentation_deeplab_instance_meta'] = instance_meta(
             inst['instance_predicted_centers'], inst['instance_predicted_centers_scores'],
             inst['instance_predicted_centers_count'], area,
             *((m['instance_class'], sc['instance_semantic_score'], sc['instance_panoptic_score'])
               if sc is not None else ()))
+        # the (N, top_k + 1) device tables the dictionaries are built from: export.instance_outputs ranks
+        # the instances on the device from these instead of reading the dictionaries
+        meta.device_tables = {'area': area, 'instance_class': m['instance_class'],
+                              'panoptic_score': sc['instance_panoptic_score'] if sc is not None else None}
         if orientation is not None:
             # instances of a class that carries orientations (semantic_class_has_orientation,
             # /root/reference/emsanet/decoder.py:151 <- model.py:43)

@@ -706,6 +706,87 @@ int emsa_adam_step(float* param, const float* grad, float* exp_avg, float* exp_a
                    const double* hyper, const double* state, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Inference output packing (csrc/export.hip): the `scannet-semantic`, `scannet-instance`,
+ * `scannet-panoptic` and `mapping` formats of /root/reference/inference_dataset.py:139-552, formed on
+ * the device from the post-processed prediction, so that only the packed bytes go to the host.
+ * Rules and their reference lines: emsanet_amd/export.py; NumPy restatement: tests/export_reference.py.
+ *
+ *   emsa_export_pack   ONE launch over a HOST table of n_jobs <= EMSA_EXPORT_MAX_JOBS jobs (grid.y =
+ *       job, read during the call).  A job reads one or two source maps [n][h][w] -- labels in the type
+ *       named by EMSA_LABEL_I64 / _I32 / _U8, scores float -- and writes one dense output [n][H][W]
+ *       (BGR: [n][H][W][3]); dst 16-byte aligned.  (h, w) != (H, W): nearest neighbour, source index
+ *       floor(dst * in / out) in float as emsa_nearest_fwd_t.  n * H * W and n * h * w < 2^31 - 4.
+ *       Class table of a job: lut != NULL: uint8[lut_size] (DEVICE); lut == NULL and lut_size > 0: the
+ *       identity on [0, lut_size); lut_size == 0: no table and no bound.  A value outside the table
+ *       packs as 0 and adds 1 to counters[EMSA_EXPORT_CAUSE_LUT].
+ *         EMSA_EXPORT_LABEL_U8         uint8    lut[src0 + add]   (lut_size in [1, 256] without a table)
+ *         EMSA_EXPORT_PANOPTIC_BGR     uint8 x3 B = inst & 0xFF, G = inst >> 8, R = lut[sem];
+ *                                      divisor == 0: sem = src0, inst = src1; divisor > 0: src0 is a
+ *                                      panoptic id, sem = id / divisor, inst = id % divisor (a negative
+ *                                      id counts as EMSA_EXPORT_CAUSE_LUT and packs as 0).  A class
+ *                                      outside [0, 255] adds to counters[EMSA_EXPORT_CAUSE_CLASS], an
+ *                                      instance outside [0, 65535] to [EMSA_EXPORT_CAUSE_INSTANCE]; the
+ *                                      low bits are stored.
+ *         EMSA_EXPORT_SEM_INST_U16     uint16   (lut[src0 + add] * 1000 + src1) mod 2^16; a value
+ *                                      outside [0, 65535] adds to counters[EMSA_EXPORT_CAUSE_WRAP]
+ *         EMSA_EXPORT_CLASS_SCORE_F32  float    (float)lut[src0 + add] + clamp(src1, 0, 0.999f) as ONE
+ *                                      fp32 add (NaN scores stay NaN); lut_size == 0: (float)(src0 + add)
+ *       depth != NULL (not with CLASS_SCORE_F32): raw depth [n][H][W], EMSA_LABEL_U16 or
+ *       EMSA_EXPORT_DEPTH_F32; where depth > max_depth class and instance are 0 (after the table, before
+ *       the BGR / wrap checks).  uint16 depth compares exactly (as in double); float depth compares in
+ *       float with max_depth rounded to float -- NumPy's rule for either array type and a Python float.
+ *       counters: int64[EMSA_EXPORT_CAUSES] (DEVICE), added to.
+ *       Stores are 4 / 8 / 12 / 16 bytes per thread = 4 consecutive pixels of the FLAT output (row
+ *       starts of a uint8 map of odd width are not dword aligned, so groups are not formed per row);
+ *       the up to 3 pixels behind the last whole group are stored one by one.  Sources of the output's
+ *       size whose address allows it are read with one vector load per map.
+ *   emsa_export_instance_ranks   area, instance_class int32[n][slots] (the per-instance tables of the
+ *       panoptic post-processing; class WITHOUT void, -1 = none).  Per sample, over ids 1 ... slots - 1
+ *       in ascending order (the order /root/reference/inference_dataset.py:420-423 enumerates the
+ *       meta): rank[n][slots] = position among the ids with area > 0, -1 for the others and for id 0;
+ *       by_rank[n][slots] = the id at each rank, class_by_rank = lut[class + 1] at each rank (table as
+ *       above; -1 behind the last rank); count[n]; start[n + 1] = running sum of count (start[n] =
+ *       total).  One workgroup.  n <= 65535, slots in [2, 65536].
+ *   emsa_export_instance_masks   stack uint8[total][H][W]: plane start[i] + r = 255 where the instance
+ *       map of sample i ([n][h][w], EMSA_LABEL_*; nearest rule as above) carries the id of rank r, else
+ *       0, for r < count[i]; planes at or behind `total` are not written.  One launch; with start /
+ *       count of emsa_export_instance_ranks and total = start[n] every byte of the stack is written.
+ * ------------------------------------------------------------------------------------------ */
+#define EMSA_EXPORT_MAX_JOBS 16
+#define EMSA_EXPORT_LABEL_U8 0
+#define EMSA_EXPORT_PANOPTIC_BGR 1
+#define EMSA_EXPORT_SEM_INST_U16 2
+#define EMSA_EXPORT_CLASS_SCORE_F32 3
+#define EMSA_EXPORT_DEPTH_F32 5         /* depth_dtype beside EMSA_LABEL_U16 */
+#define EMSA_EXPORT_CAUSES 4
+#define EMSA_EXPORT_CAUSE_LUT 0
+#define EMSA_EXPORT_CAUSE_CLASS 1
+#define EMSA_EXPORT_CAUSE_INSTANCE 2
+#define EMSA_EXPORT_CAUSE_WRAP 3
+typedef struct EmsaExportJob {
+  const void* src0;
+  const void* src1;
+  const void* depth;
+  const uint8_t* lut;
+  void* dst;
+  int64_t divisor;
+  double max_depth;
+  int32_t kind, src0_dtype, src1_dtype, depth_dtype;
+  int32_t lut_size, add;
+  int32_t h, w;
+} EmsaExportJob;
+int emsa_export_pack(const EmsaExportJob* jobs, int32_t n_jobs, int32_t n, int32_t H, int32_t W,
+                     int64_t* counters, void* stream);
+int emsa_export_instance_ranks(const int32_t* area, const int32_t* instance_class, const uint8_t* lut,
+                               int32_t lut_size, int32_t n, int32_t slots, int32_t* rank,
+                               int32_t* by_rank, int32_t* class_by_rank, int32_t* count,
+                               int32_t* start, int64_t* counters, void* stream);
+int emsa_export_instance_masks(const void* instance, int32_t instance_dtype, int32_t n, int32_t h,
+                               int32_t w, int32_t H, int32_t W, const int32_t* rank, int32_t slots,
+                               const int32_t* count, const int32_t* start, int32_t total,
+                               uint8_t* stack, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * 16-bit convolution family (BASELINE configs[2] bf16 mixed-precision training, configs[4] 16-bit
  * inference; the reference trains / times fp32 and fp16-TensorRT, README.md:176-181).
  *
