@@ -13,12 +13,18 @@ def __getattr__(name):
         from .decoder import get_decoders
         return get_decoders
     if name in ('MeanIntersectionOverUnion', 'PanopticQuality', 'panoptic_targets', 'SceneAccuracy',
-                'MeanAbsoluteAngularError'):
+                'MeanAbsoluteAngularError', 'MeanAbsoluteNormalError'):
         from . import metrics
         return getattr(metrics, name)
     if name in ('TrainingTargetGenerator', 'orientation_table'):
         from . import targets
         return getattr(targets, name)
+    if name == 'NormalLoss':
+        from .loss import NormalLoss
+        return NormalLoss
+    if name == 'NormalPostprocessing':
+        from .postprocessing import NormalPostprocessing
+        return NormalPostprocessing
     if name == 'ValidationEvaluator':
         from .evaluation import ValidationEvaluator
         return ValidationEvaluator

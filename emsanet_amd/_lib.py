@@ -58,6 +58,10 @@ class EmsaExportJob(Structure):
                 ('w', c_int32)]
 
 
+class EmsaNormalScale(Structure):
+    _fields_ = [('scale', c_int32), ('reserved', c_int32), ('out', c_void_p)]
+
+
 _P = c_void_p          # device pointers travel as integers (tensor.data_ptr())
 _GP = POINTER(EmsaConvGeom)
 _TP = POINTER(EmsaTargetScale)
@@ -193,6 +197,15 @@ SIGNATURES = {
     'emsa_augment_apply': (c_int, [_P, _P, _P, c_int32, _P, c_int32, _P] + [c_int32] * 5 +
                            [_P, _P, _P, _P, c_float, _P, _P, c_float, c_float, c_int32, c_int32, _P]),
     'emsa_augment_orientations': (c_int, [_P, _P, _P, c_int32, c_int32, _P]),
+    'emsa_normal_l1_blocks': (c_int, [c_int64]),
+    'emsa_normal_l1_fwd': (c_int, [_P, c_int32, _P, c_int32, c_int64, c_int64, _P, _P, _P]),
+    'emsa_normal_l1_bwd': (c_int, [_P, c_int32, _P, c_int32, c_int64, c_int64, _P, _P, _P, c_int32, _P]),
+    'emsa_normal_targets': (c_int, [_P, c_int32, c_int32, c_int32, c_int32, POINTER(EmsaNormalScale),
+                                    c_int32, _P]),
+    'emsa_augment_normal': (c_int, [_P, c_int32, _P] + [c_int32] * 5 + [_P, _P]),
+    'emsa_normal_unit': (c_int, [_P, c_int32, c_int64, _P, _P]),
+    'emsa_normal_angular_error': (c_int, [_P, c_int32, c_int32, c_int32, c_int32, _P, c_int32, c_int32,
+                                          c_int32, _P, _P, _P]),
     'emsa_normalize_rgb': (c_int, [_P, _P, c_int32, c_int32, c_int32, c_float, _P, _P, _P]),
     'emsa_normalize_depth': (c_int, [_P, _P, c_int64, c_float, c_float, c_int32, _P]),
     'emsa_sgd_nesterov': (c_int, [_P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_int32,

@@ -80,6 +80,8 @@ _DEFAULTS = {
     'instance_center_loss': ('mse', 750),
     'instance_no_multiscale_supervision': (False, 757),
     'orientation_kappa': (1.0, 766),
+    'normal_loss': ('l1', 775),
+    'normal_no_multiscale_supervision': (False, 782),
     'scene_loss_label_smoothing': (0.1, 791),
     # optimizer / schedule
     'optimizer': ('sgd', 661),

@@ -5,9 +5,10 @@ Training augmentation on device: the random part of the reference's training pre
 `RandomCrop(input_height, input_width)`, `RandomHSVJitter(10/180, 20/255, 50/255)`,
 `RandomHorizontalFlip(0.5)` -- fused with `NormalizeRGB` / `NormalizeDepth` + HWC->CHW
 (preprocessing.py:216-226).  `TrainingAugmenter.apply` replaces them with two kernel launches for the
-whole batch and all of its maps (three with an orientation table; csrc/augment.hip), so a loader ships
-un-augmented raw frames.  `resize_normalize` is the deterministic validation twin
-(`Resize(validation_input_height, validation_input_width)`, preprocessing.py:147-154).
+whole batch and all of its maps (one more with an orientation table, one more with a normal map;
+csrc/augment.hip, csrc/normal.hip), so a loader ships un-augmented raw frames.  `resize_normalize` is
+the deterministic validation twin (`Resize(validation_input_height, validation_input_width)`,
+preprocessing.py:147-154).
 
 Rules; [U] = the un-vendored `nicr_mt_scene_analysis` library / cv2 is the only source and the rule is
 restated here (tests/augment_reference.py is the NumPy restatement):
@@ -41,7 +42,13 @@ sample's parameter row (Hr, Wr, cy, cx, flip, dh, ds, dv).
   orientations    for a flipped sample theta -> (2 pi - theta) mod 2 pi in [0, 2 pi), in fp32 with
                   2 pi = 6.2831855: a = 2pi - theta; a -= 2pi * floor(a / 2pi); a += 2pi if a < 0;
                   a -= 2pi if a >= 2pi.  NaN stays NaN.  [U]
-  scene           passes through.  The 'normal' task is refused (a flip would negate a component).
+  normals         with `with_normal=True`: float32 (N,Hs,Ws,3) or (N,3,Hs,Ws), channel 0 the image-x
+                  component, (0,0,0) = invalid.  The composed index and the nearest rule of depth and the
+                  labels; values are copied, and channel 0 is negated on a flipped sample.  Nothing is
+                  interpolated or re-normalised, so an invalid pixel stays (+-0, 0, 0): still invalid.
+                  One more launch (csrc/normal.hip).  [U]
+  scene           passes through.  Without `with_normal=True` the 'normal' task is refused (a flip has to
+                  negate a component: the caller opts in to the rule above).
 
 Parameters are counter-based and integer, so the NumPy restatement reproduces them bit for bit:
   hash            lowbias32(x): x ^= x >> 16; x *= 0x7FEB352D; x ^= x >> 15; x *= 0x846CA68B; x ^= x >> 16
@@ -64,7 +71,7 @@ import torch
 from . import _lib
 from ._lib import check
 from .functional import _stream
-from .postprocessing import RGB_MEAN, RGB_STD
+from .postprocessing import RGB_MEAN, RGB_STD, normal_map
 
 _LABEL_DTYPES = {torch.int64: 0, torch.int32: 1, torch.uint8: 2, torch.int16: 3, torch.uint16: 4}   # EMSA_LABEL_*
 MAX_SIDE = 4096
@@ -91,13 +98,15 @@ class TrainingAugmenter:
     args: `input_height`, `input_width`, `aug_scale_min`, `aug_scale_max`, `input_modalities`, `tasks`.
     depth_stats = (mean, std) of the depth normalisation.  hsv_jitter: the amplitudes of (dh, ds, dv);
     all three 0 removes the stage.  flip_p: the probability of a flip.  ring: the outputs rotate over
-    that many sets, so the results of the previous ring - 1 calls stay valid.
+    that many sets, so the results of the previous ring - 1 calls stay valid.  with_normal: augment
+    batch['normal'] too when 'normal' is in `tasks` (refused otherwise).
 
     batch: 'rgb' uint8 (N,Hs,Ws,3) and / or 'depth' uint16 (N,Hs,Ws) as `input_modalities` says,
     'semantic' (with the semantic task) and 'instance' (instance / orientation) label maps (N,Hs,Ws) of
     int64, int32, int16, uint16 or uint8, 'orientations' float32 (N, max_instances) (orientation),
-    'scene' (N,) -- all on the GPU.  Returned: 'rgb' float32 (N,3,H,W), 'depth' float32 (N,1,H,W), the
-    label maps (N,H,W) in their own type, the orientation table and 'scene', ready for
+    'scene' (N,), 'normal' float32 (N,Hs,Ws,3) or (N,3,Hs,Ws) (with_normal) -- all on the GPU.
+    Returned: 'rgb' float32 (N,3,H,W), 'depth' float32 (N,1,H,W), the label maps (N,H,W) in their own
+    type, the orientation table, 'scene' and 'normal' float32 (N,3,H,W) over (N,H,W,3) memory, ready for
     `EMSANet.forward` and `TrainingTargetGenerator.generate`.
 
     `apply` only launches kernels on the current stream: no host copy, no synchronisation and no
@@ -106,9 +115,9 @@ class TrainingAugmenter:
     replay draws fresh parameters."""
 
     def __init__(self, args, depth_stats=(0.0, 1.0), seed=0, hsv_jitter=DEFAULT_HSV_JITTER, flip_p=0.5,
-                 ring=2):
+                 ring=2, with_normal=False):
         tasks = tuple(args.tasks)
-        if 'normal' in tasks:
+        if 'normal' in tasks and not with_normal:
             raise NotImplementedError(f"{_WHO}: the 'normal' task is not augmented (a horizontal flip "
                                       "would have to negate a component of the normals)")
         self.height, self.width = int(args.input_height), int(args.input_width)
@@ -118,6 +127,7 @@ class TrainingAugmenter:
         self.with_instance = 'instance' in tasks or 'orientation' in tasks
         self.with_orientation = 'orientation' in tasks
         self.with_scene = 'scene' in tasks
+        self.with_normal = 'normal' in tasks and bool(with_normal)
         self.depth_stats = (float(depth_stats[0]), float(depth_stats[1]))
         self.hsv_jitter = tuple(float(a) for a in hsv_jitter)
         if len(self.hsv_jitter) != 3 or any(not 0.0 <= a <= 1.0 for a in self.hsv_jitter):
@@ -154,14 +164,14 @@ class TrainingAugmenter:
 
     def _inputs(self, batch, who):
         """the tensors the configuration asks for, checked: (rgb, depth, [labels], orientations, scene,
-        n, hs, ws, device)"""
+        n, hs, ws, maps, normal); normal = (tensor, chw flag) or None"""
         def tensor(key):
             t = batch.get(key)
             if not torch.is_tensor(t):
                 raise TypeError(f"{who}: batch['{key}'] must be a tensor")
             return t
 
-        rgb = depth = orient = scene = None
+        rgb = depth = orient = scene = normal = None
         shape = None
         maps = []
 
@@ -195,6 +205,15 @@ class TrainingAugmenter:
             same(key, t)
             labels.append((key, t))
             maps.append((key, t))
+        if self.with_normal:
+            t, chw, s = normal_map(batch.get('normal'), who, "batch['normal']",
+                                   hw=None if shape is None else shape[1:])
+            if shape is not None and s != shape:
+                raise ValueError(f"{who}: batch['normal'] has shape {tuple(t.shape)}, the other maps {shape}")
+            shape = s
+            normal = (t, chw)
+            # (contiguous itself, or a channels-last view of contiguous (N,H,W,3) memory)
+            maps.append(('normal', t if t.is_contiguous() else t.permute(0, 2, 3, 1)))
         if shape is None:
             raise ValueError(f"{who}: neither an input modality nor a label map to work on")
         n, hs, ws = shape
@@ -208,7 +227,7 @@ class TrainingAugmenter:
             if tuple(scene.shape) != (n,):
                 raise ValueError(f"{who}: batch['scene'] must be an ({n},) tensor")
             maps.append(('scene', scene))
-        return rgb, depth, labels, orient, scene, n, hs, ws, maps
+        return rgb, depth, labels, orient, scene, n, hs, ws, maps, normal
 
     @staticmethod
     def _on_device(maps, who):
@@ -259,12 +278,14 @@ class TrainingAugmenter:
                 s['orientations'] = torch.empty_like(orient)
             if scene is not None:
                 s['scene'] = torch.empty_like(scene)
+            if self.with_normal:
+                s['normal'] = torch.empty((n, h, w, 3), device=device, dtype=torch.float32).permute(0, 3, 1, 2)
             slots.append(s)
         r = self._rings[key] = [0, slots]
         return r
 
     def _run(self, batch, h, w, table, draw, hsv, who):
-        rgb, depth, labels, orient, scene, n, hs, ws, maps = self._inputs(batch, who)
+        rgb, depth, labels, orient, scene, n, hs, ws, maps, normal = self._inputs(batch, who)
         if draw:
             self.check_size(hs, ws)
         elif not (1 <= hs <= MAX_SIDE and 1 <= ws <= MAX_SIDE and 1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
@@ -303,6 +324,11 @@ class TrainingAugmenter:
                                               slot['params'].data_ptr(), n, orient.shape[1], st),
                   'emsa_augment_orientations')
             out['orientations'] = slot['orientations']
+        if normal is not None:
+            check(L.emsa_augment_normal(normal[0].data_ptr(), 1 if normal[1] else 0,
+                                        slot['params'].data_ptr(), n, hs, ws, h, w,
+                                        slot['normal'].data_ptr(), st), 'emsa_augment_normal')
+            out['normal'] = slot['normal']
         if scene is not None:
             out['scene'] = slot['scene']
             out['scene'].copy_(scene)         # (a copy: the caller may refill its buffer)
@@ -326,7 +352,7 @@ class TrainingAugmenter:
         height, width = int(height), int(width)
         if not (1 <= height <= MAX_SIDE and 1 <= width <= MAX_SIDE):
             raise ValueError(f"{who}: {height}x{width}; sides in [1, {MAX_SIDE}]")
-        *_x, n, _hs, _ws, maps = self._inputs(batch, who)
+        *_x, n, _hs, _ws, maps, _normal = self._inputs(batch, who)
         device = self._on_device(maps, who)
         key = (device, n, height, width)
         table = self._identity.get(key)

@@ -93,6 +93,14 @@ static inline void emsa_zero_async(void* p, size_t bytes, hipStream_t st) {
   hipLaunchKernelGGL(emsa_zero_kernel, dim3((int)blocks), dim3(256), 0, st, (uint32_t*)p, words);
 }
 
+// Source index of torch.nn.functional.interpolate(mode='nearest'): floor(dst * in / out) in float
+// arithmetic, clamped (the 'nearest' up-sampling kernels, the full-resolution export, the normal metric).
+__device__ __forceinline__ int emsa_nearest_src(int o, int in, int out) {
+  const float scale = (float)in / (float)out;
+  const int i = (int)floorf((float)o * scale);
+  return i < in - 1 ? i : in - 1;
+}
+
 // counter-based hash shared with oracle/emsanet_oracle.py (_lowbias32)
 __host__ __device__ __forceinline__ uint32_t emsa_lowbias32(uint32_t x) {
   x ^= x >> 16;

@@ -17,13 +17,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kMaxBlocks = 2048;          // ~8 workgroups per CU, grid-stride beyond
 
-// same arithmetic as nearest_src of pointwise.hip (torch's 'nearest': floor(dst * in / out) in float)
-__device__ __forceinline__ int nearest_src(int o, int in, int out) {
-  const float scale = (float)in / (float)out;
-  const int i = (int)floorf((float)o * scale);
-  return i < in - 1 ? i : in - 1;
-}
-
 // the job as the kernel sees it (EmsaExportJob with the host-side decisions taken)
 struct PackJob {
   const void* src0;
@@ -109,16 +102,16 @@ __global__ __launch_bounds__(kThreads) void export_pack_kernel(const PackTable t
     } else if (row4) {
       const int img = p0 / hw, r = p0 - img * hw;
       const int y = r / W, x = r - y * W;
-      const int base = img * shw + nearest_src(y, j.h, H) * j.w;
+      const int base = img * shw + emsa_nearest_src(y, j.h, H) * j.w;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) idx[k] = base + nearest_src(x + k, j.w, W);
+      for (int k = 0; k < 4; ++k) idx[k] = base + emsa_nearest_src(x + k, j.w, W);
     } else {
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const int p = p0 + k;
         const int img = p / hw, r = p - img * hw;
         const int y = r / W, x = r - y * W;
-        idx[k] = k < valid ? img * shw + nearest_src(y, j.h, H) * j.w + nearest_src(x, j.w, W) : -1;
+        idx[k] = k < valid ? img * shw + emsa_nearest_src(y, j.h, H) * j.w + emsa_nearest_src(x, j.w, W) : -1;
       }
     }
 #pragma unroll
@@ -317,7 +310,7 @@ __global__ __launch_bounds__(kThreads) void export_masks_kernel(
     for (int k = 0; k < kPer; ++k) {
       const int p = g * kPer + k;
       const int y = p / W, x = p - y * W;
-      const long id = (long)src[nearest_src(y, h, H) * w + nearest_src(x, w, W)];
+      const long id = (long)src[emsa_nearest_src(y, h, H) * w + emsa_nearest_src(x, w, W)];
       r[k] = (id >= 0 && id < slots) ? rk[id] : -1;
     }
     for (int q = 0; q < planes; ++q) {

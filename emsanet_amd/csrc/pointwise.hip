@@ -2249,13 +2249,8 @@ __global__ void bilinear_bwd_kernel(const T* __restrict__ dy, float* __restrict_
 
 // 'nearest' up-sampling of the pyramid-pooling branches (`--upsampling-context-module nearest`,
 // /root/reference/emsanet/args.py:250-256; torch.nn.functional.interpolate(mode='nearest'): source index
-// floor(dst * in / out) in float arithmetic, clamped).  Backward: gather, one thread per dx element over
-// the window of outputs that map to it, fixed order.
-__device__ __forceinline__ int nearest_src(int o, int in, int out) {
-  const float scale = (float)in / (float)out;
-  const int i = (int)floorf((float)o * scale);
-  return i < in - 1 ? i : in - 1;
-}
+// floor(dst * in / out) in float arithmetic, clamped: emsa_nearest_src of common.h).  Backward: gather,
+// one thread per dx element over the window of outputs that map to it, fixed order.
 template <typename T>
 __global__ void nearest_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, int n, int ih, int iw,
                                    int oh, int ow, int c, int ld_y) {
@@ -2267,7 +2262,7 @@ __global__ void nearest_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, i
     const int xo = (int)(r % ow); r /= ow;
     const int yo = (int)(r % oh);
     const int img = (int)(r / oh);
-    const int yi = nearest_src(yo, ih, oh), xi = nearest_src(xo, iw, ow);
+    const int yi = emsa_nearest_src(yo, ih, oh), xi = emsa_nearest_src(xo, iw, ow);
     emsa_st1(y + (((long)img * oh + yo) * ow + xo) * ld_y + ch,
              emsa_ld1(x + (((long)img * ih + yi) * iw + xi) * c + ch));
   }
@@ -2292,7 +2287,7 @@ __global__ void nearest_bwd_kernel(const T* __restrict__ dy, float* __restrict__
     const int yi = (int)(r % ih);
     const int img = (int)(r / ih);
     const T* b = dy + (long)img * oh * ow * ld_dy + ch;
-    // outputs o with nearest_src(o) == yi lie in [yi * oh / ih, (yi + 1) * oh / ih) up to float
+    // outputs o with emsa_nearest_src(o) == yi lie in [yi * oh / ih, (yi + 1) * oh / ih) up to float
     // rounding: one output of margin on both sides, the membership test decides
     const float ry = (float)oh / (float)ih, rx = (float)ow / (float)iw;
     int y_lo = (int)((float)yi * ry) - 1, y_hi = (int)((float)(yi + 1) * ry) + 1;
@@ -2301,9 +2296,9 @@ __global__ void nearest_bwd_kernel(const T* __restrict__ dy, float* __restrict__
     x_lo = x_lo < 0 ? 0 : x_lo; x_hi = x_hi > ow - 1 ? ow - 1 : x_hi;
     float a = 0.f;
     for (int yo = y_lo; yo <= y_hi; ++yo) {
-      if (nearest_src(yo, ih, oh) != yi) continue;
+      if (emsa_nearest_src(yo, ih, oh) != yi) continue;
       for (int xo = x_lo; xo <= x_hi; ++xo)
-        if (nearest_src(xo, iw, ow) == xi) a += emsa_ld1(b + ((long)yo * ow + xo) * ld_dy);
+        if (emsa_nearest_src(xo, iw, ow) == xi) a += emsa_ld1(b + ((long)yo * ow + xo) * ld_dy);
     }
     dx[i] = a;
   }

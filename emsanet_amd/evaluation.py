@@ -24,6 +24,8 @@ Keys of `compute()` (the reference's names without the `valid_` prefix):
   panoptic_deeplab_semantic_miou         panoptic_segmentation_deeplab_semantic_idx (with void)
                                          against batch['semantic'], void ignored
   panoptic_mae_deeplab_deg / _rad        angular error over the segments the panoptic PQ matched
+  normal_mae_deg / _rad                  mean angle between the raw `normal_output` and the valid vectors
+                                         of batch['normal'] (`metrics.MeanAbsoluteNormalError`)
 Only the keys whose task is in `args.tasks` / `args.enable_panoptic` are present.
 
 [U] (the metric library is not vendored; each rule is restated in tests/evaluation_reference.py):
@@ -37,7 +39,10 @@ Only the keys whose task is in `args.tasks` / `args.enable_panoptic` are present
   * `panoptic_mae_deeplab`: only instances of a class with `classes_use_orientations` are compared
     (the keep table of `PanopticPostprocessing`)
   * label maps larger than the network output: every map is read from its `<key>_fullres` entry; the
-    orientation channels, which have none, are resampled with nearest neighbour.
+    orientation channels, which have none, are resampled with nearest neighbour.  The normal target is
+    batch['normal_fullres'] when the batch has it, batch['normal'] otherwise; a smaller `normal_output`
+    is read with nearest neighbour.
+  * `normal_mae`: the mean over pixels of atan2(|p x t|, p . t), which needs no unit length.
 
 Not built: `panoptic_*_with_gt_deeplab_*`.  Nothing in the reference's tree says what "with gt" means
 for the panoptic helper, so no such key is guessed.  Validation losses are out of scope here.
@@ -47,8 +52,8 @@ import torch
 from . import _lib
 from . import functional as Fn
 from ._lib import check
-from .metrics import (_LABEL_DTYPES, MeanAbsoluteAngularError, MeanIntersectionOverUnion, PanopticQuality,
-                      SceneAccuracy, _label_map)
+from .metrics import (_LABEL_DTYPES, MeanAbsoluteAngularError, MeanAbsoluteNormalError,
+                      MeanIntersectionOverUnion, PanopticQuality, SceneAccuracy, _label_map)
 from .postprocessing import thing_table
 
 _KEEP_KEY = 'orientations_panoptic_segmentation_deeplab_instance_keep'
@@ -71,6 +76,7 @@ class ValidationEvaluator:
         self.with_instance = 'instance' in tasks
         self.with_orientation = 'orientation' in tasks
         self.with_panoptic = bool(getattr(args, 'enable_panoptic', False))
+        self.with_normal = 'normal' in tasks
         self.n_classes = len(labels) + 1                                  # with void
         self.is_thing = (False,) + tuple(bool(t) for t in labels.classes_is_thing)
         self.max_instances = int(max_instances)
@@ -90,6 +96,7 @@ class ValidationEvaluator:
         self.panoptic_miou = MeanIntersectionOverUnion(self.n_classes, True) if self.with_panoptic else None
         self.panoptic_mae = MeanAbsoluteAngularError() if self.with_panoptic and self.with_orientation \
             else None
+        self.normal_mae = MeanAbsoluteNormalError() if self.with_normal else None
         # whether the prediction carries a grouping for `instance_all_with_gt`: a property of the model,
         # learnt in the first update and kept over reset() (a replayed graph runs no Python)
         self._instance_pq_seen = False
@@ -223,12 +230,17 @@ class ValidationEvaluator:
                 self.panoptic_mae.update_matched(vec, cnt, gt_table, matches, n_matches,
                                                  self.label_divisor, keep)
 
+        if self.with_normal:
+            target = batch.get('normal_fullres')
+            self.normal_mae.update(prediction['normal_output'],
+                                   target if torch.is_tensor(target) else batch['normal'])
+
     # ---- results -----------------------------------------------------------------------------------
     def _metrics(self):
         return {'semantic_miou': self.semantic_miou, 'scene': self.scene,
                 'orientation_mae_gt': self.orientation_mae_gt, 'instance_pq': self.instance_pq,
                 'panoptic_pq': self.panoptic_pq, 'panoptic_miou': self.panoptic_miou,
-                'panoptic_mae': self.panoptic_mae}
+                'panoptic_mae': self.panoptic_mae, 'normal_mae': self.normal_mae}
 
     def reset(self):
         for m in self._metrics().values():
@@ -267,4 +279,7 @@ class ValidationEvaluator:
             if self.panoptic_mae is not None:
                 m = self.panoptic_mae.compute()
                 r['panoptic_mae_deeplab_deg'], r['panoptic_mae_deeplab_rad'] = m['mae_deg'], m['mae_rad']
+        if self.with_normal:
+            m = self.normal_mae.compute()
+            r['normal_mae_deg'], r['normal_mae_rad'] = m['mae_deg'], m['mae_rad']
         return r

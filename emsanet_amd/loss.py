@@ -16,6 +16,11 @@ Training losses on device: what `task_helper.training_step` +
 * `InstanceLosses(kappa=1.0)`: MSE centre / L1 offset / von-Mises orientation in one fused pass
   (args.py:739-770).  The loss classes are in the un-vendored nicr_mt_scene_analysis library:
   PARITY UNPINNED, restated in oracle/instance_loss_oracle.py.
+* `NormalLoss(loss_name='l1')`: masked L1 on the raw maps of the normal decoder (`--normal-loss`,
+  args.py:775-780, default 'l1').  The loss class is in the un-vendored library: [U], restated in
+  tests/normal_reference.py.  Per scale: sum over the valid pixels and the 3 channels of |p - t|,
+  divided by 3 n_valid; a pixel is valid iff its target vector is not exactly (0, 0, 0); the prediction is
+  not normalised.  Gradient: g sign(p - t) / (3 n_valid) on valid pixels (sign(0) = 0), 0 elsewhere.
 * `loss_weights(args)` / `reduce_losses`: /root/reference/emsanet/loss_weighting.py:11-49
   (fixed weights, defaults 1 / 0.25 / 3 x (2 : 1) / 0.5, README.md:621-622).
 
@@ -27,7 +32,8 @@ label above n_classes (255 in a uint8 map) or a negative one -- is treated exact
 pixel adds nothing to the loss or its divisor and its gradient row is zero; no error is raised.
 A map without a single valid label gives loss 0 and an all-zero gradient.  More than 64 classes,
 a target whose element count differs from the logits' pixels and instance targets of another
-size than the predictions raise `EmsaError`.
+size than the predictions raise `EmsaError`.  A normal target must be a float32 GPU tensor of the
+prediction's size, (N,H,W,3) or (N,3,H,W): TypeError / NotImplementedError / ValueError otherwise.
 """
 import torch
 from torch.autograd import Function
@@ -36,6 +42,7 @@ from torch.autograd.function import once_differentiable
 from . import _lib
 from . import functional as Fn
 from ._lib import check
+from .postprocessing import normal_map
 
 
 class SemanticCEFunction(Function):
@@ -206,6 +213,59 @@ class InstanceLosses(torch.nn.Module):
         return res
 
 
+class NormalL1Function(Function):
+    @staticmethod
+    def forward(ctx, pred, target):
+        if not torch.is_tensor(pred) or pred.dim() != 4 or pred.shape[1] != 3:
+            raise ValueError("normal loss: the prediction must be an (N, 3, H, W) tensor")
+        n, _, h, w = pred.shape
+        target, chw, shape = normal_map(target, 'normal loss', 'the target', hw=(h, w))
+        if shape[0] != n:
+            raise ValueError(f"normal loss: target of {shape[0]} images, prediction of {n}")
+        if not pred.is_cuda or pred.device != target.device:
+            raise NotImplementedError("normal loss: the prediction must be on the GPU of the target")
+        pred = Fn.as_act(pred.float() if pred.dtype != torch.float32 else pred)
+        L = _lib.lib()
+        pixels = n * h * w
+        partial = Fn._empty((2 * L.emsa_normal_l1_blocks(pixels),), pred.device)
+        out = Fn._empty((2,), pred.device)
+        p = Fn._p
+        check(L.emsa_normal_l1_fwd(p(pred), Fn.ld_of(pred), p(target), 1 if chw else 0, h * w, pixels,
+                                   p(partial), p(out), Fn._stream()), 'emsa_normal_l1_fwd')
+        ctx.save_for_backward(pred, target, out)
+        ctx.chw = chw
+        return out[0]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        pred, target, out = ctx.saved_tensors
+        n, _, h, w = pred.shape
+        d = Fn.act_empty(n, 3, h, w, pred.device, ld=Fn.pad4(3))      # rows of 4: one 16-byte store
+        g = gout.detach().float().reshape(1).contiguous()
+        p = Fn._p
+        check(_lib.lib().emsa_normal_l1_bwd(p(pred), Fn.ld_of(pred), p(target), 1 if ctx.chw else 0,
+                                            h * w, n * h * w, p(out), p(g), p(d), Fn.pad4(3),
+                                            Fn._stream()), 'emsa_normal_l1_bwd')
+        return d, None
+
+
+class NormalLoss(torch.nn.Module):
+    """[U] the normal task's loss: `forward(input_scales, target_scales)` -> [(loss_scale_i, ), ...] like
+    `CrossEntropyLossSemantic`.  Predictions (N,3,H_s,W_s) raw decoder maps, targets float32
+    (N,H_s,W_s,3) or (N,3,H_s,W_s) with (0,0,0) = invalid (`TrainingTargetGenerator` makes them)."""
+
+    def __init__(self, loss_name='l1'):
+        super().__init__()
+        if loss_name != 'l1':
+            raise NotImplementedError(f"normal loss '{loss_name}': only the reference default 'l1' "
+                                      "(emsanet/args.py:775-780)")
+        self.loss_name = loss_name
+
+    def forward(self, input_scales, target_scales):
+        return [(NormalL1Function.apply(x, t),) for x, t in zip(input_scales, target_scales)]
+
+
 def loss_weights(args):
     """flat per-loss weights from the task weights, /root/reference/emsanet/loss_weighting.py:15-49:
     orientation keeps its own task weight, the instance weight is multiplied into the
@@ -252,7 +312,10 @@ class TrainingLosses(torch.nn.Module):
         'semantic'  [ (N,H_s,W_s) int, 0 = void ]
         'instance'  [ dict(center (N,1,H_s,W_s), offset (N,2,H_s,W_s), foreground (N,H_s,W_s),
                            orientation (N,H_s,W_s) rad, orientation_foreground (N,H_s,W_s)) ]
+        'normal'    [ (N,H_s,W_s,3) or (N,3,H_s,W_s) float32, (0,0,0) = invalid ]  (with the task)
         'scene'     (N,) int, 0 = void
+    With 'normal' in `args.tasks` the normal decoder's (output, side outputs) come between the instance
+    decoder's and the scene logits, the order of the model's decoders.
     (how the reference's batch dictionary names the down-scaled targets is defined by the
     un-vendored library's preprocessing: [U], so the caller maps them.)"""
 
@@ -268,6 +331,9 @@ class TrainingLosses(torch.nn.Module):
         self.scene = CrossEntropyLossScene(n_scene_classes,
                                            label_smoothing=args.scene_loss_label_smoothing)
         self.instance = InstanceLosses(args.orientation_kappa, args.instance_center_loss)
+        if 'normal' in self.tasks:
+            self.normal_multiscale = not getattr(args, 'normal_no_multiscale_supervision', False)
+            self.normal = NormalLoss(getattr(args, 'normal_loss', 'l1'))
 
     def forward(self, outputs, targets):
         """-> (total, dict of unweighted per-task losses summed over the scales)"""
@@ -283,6 +349,8 @@ class TrainingLosses(torch.nn.Module):
                 outputs.append((merged['semantic_output'], merged['semantic_side_outputs']))
             if 'instance' in self.tasks or 'orientation' in self.tasks:
                 outputs.append((merged['instance_output'], merged['instance_side_outputs']))
+            if 'normal' in self.tasks:
+                outputs.append((merged['normal_output'], merged['normal_side_outputs']))
             if 'scene' in self.tasks:
                 outputs.append((merged['scene_output'],))
         outputs = list(outputs)
@@ -309,6 +377,11 @@ class TrainingLosses(torch.nn.Module):
                 for k, v in r.items():
                     acc[k] = v if k not in acc else acc[k] + v
             losses.update(acc)
+        if 'normal' in self.tasks:
+            full, side = next(it)
+            xs = [full] + (list(side) if self.normal_multiscale else [])
+            ls = self.normal(xs, targets['normal'][:len(xs)])
+            losses['normal'] = torch.stack([l[0] for l in ls]).sum()
         if 'scene' in self.tasks:
             logits = next(it)[0]
             losses['scene'] = self.scene(logits, targets['scene'])

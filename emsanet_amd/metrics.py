@@ -3,8 +3,8 @@
 Validation metrics on device: mean IoU and panoptic quality, the two values the reference keeps its
 checkpoints by (`valid_semantic_miou`, `valid_panoptic_all_deeplab_pq`: /root/reference/main.py:229,
 emsanet/args.py:1054), and the other checkpoint keys of the reference's evaluation commands: scene
-accuracy (`bacc`) and the mean absolute angular error of the orientations (`mae_gt_deg`,
-`panoptic_mae_deeplab_deg`).  `emsanet_amd.evaluation.ValidationEvaluator` composes them.
+accuracy (`bacc`), the mean absolute angular error of the orientations (`mae_gt_deg`,
+`panoptic_mae_deeplab_deg`) and that of the surface normals (`normal_mae_deg`).  `emsanet_amd.evaluation.ValidationEvaluator` composes them.
 
 The reference takes them from `metric.MeanIntersectionOverUnion` / `metric.PanopticQuality` of the
 un-vendored `nicr_mt_scene_analysis` library.  The classes here keep that surface
@@ -21,10 +21,12 @@ import torch
 from . import _lib
 from ._lib import check
 from .functional import _stream
-from .postprocessing import thing_table
+from . import functional as Fn
+from .postprocessing import normal_map, thing_table
 
 _LABEL_DTYPES = {torch.int64: 0, torch.int32: 1, torch.uint8: 2}       # EMSA_LABEL_*
 IOU_ONE = 1 << 40                                                      # fixed point of iou_sum
+NORMAL_ANGLE_ONE = 1 << 20          # EMSA_NORMAL_ANGLE_ONE: fixed point of the normal error sum, 1 / rad
 
 
 def _label_map(t, name, what):
@@ -398,6 +400,74 @@ class MeanAbsoluteAngularError:
         if n == 0:
             return {'mae_rad': float('nan'), 'mae_deg': float('nan')}
         rad = total / ANGLE_ONE / n
+        return {'mae_rad': rad, 'mae_deg': math.degrees(rad)}
+
+
+class MeanAbsoluteNormalError:
+    """[U] `valid_normal_mae_*`: the mean over all valid pixels of all updates of the angle between the
+    predicted and the ground-truth normal, atan2(|p x t|, p . t) in [0, pi] -- well conditioned near 0 and
+    pi, needs neither vector at unit length and equals acos of the cosine similarity.
+
+    `update(pred, target)`: pred float (N,3,h,w) on the GPU, the raw `normal_output` (any length);
+    target float32 (N,H,W,3) or (N,3,H,W), (0,0,0) = invalid (not compared).  Where the target is larger
+    than the prediction, the prediction is read with nearest neighbour (source index floor(y * h / H), the
+    rule of `evaluation`).  The angle is computed in fp32, rounded once to 2^-20 rad (at most 4.8e-7 rad
+    per pixel; room for more than 10^12 pixels in the int64 sum) and added as an integer, so the state
+    does not depend on the launch geometry or on the order of the updates; the count is exact.  One
+    launch on the current stream, no host copy, no allocation after the first call.
+
+    `compute()` -> {'mae_rad', 'mae_deg'}: NaN, not 0.0, when nothing was compared (ranked "lower is
+    better").  It is the one host read and raises ValueError if a prediction was not finite (such a pixel
+    is not compared)."""
+
+    def __init__(self):
+        self._state = None                      # int64 [3]: error sum (2^-20 rad), count, int32 flag
+
+    def _buffers(self, device):
+        if self._state is None or self._state.device != device:
+            self._state = torch.zeros(3, device=device, dtype=torch.int64)
+        return self._state
+
+    def update(self, pred, target):
+        name = 'MeanAbsoluteNormalError.update'
+        if not torch.is_tensor(pred):
+            raise TypeError(f"{name}: pred must be a tensor")
+        if not pred.dtype.is_floating_point:
+            raise TypeError(f"{name}: pred has dtype {pred.dtype}; a floating-point (N, 3, h, w) map")
+        if pred.dim() != 4 or pred.shape[1] != 3:
+            raise ValueError(f"{name}: pred has shape {tuple(pred.shape)}; expected (N, 3, h, w)")
+        target, chw, (n, th, tw) = normal_map(target, name, 'target')
+        if not pred.is_cuda:
+            raise NotImplementedError(f"{name}: pred is a CPU tensor; the metrics count on the GPU only")
+        if pred.shape[0] != n or pred.device != target.device:
+            raise ValueError(f"{name}: pred {tuple(pred.shape)} on {pred.device} vs target of {n} images on "
+                             f"{target.device}")
+        pred = Fn.as_act(pred if pred.dtype == torch.float32 else pred.float())
+        s = self._buffers(pred.device)
+        check(_lib.lib().emsa_normal_angular_error(
+            pred.data_ptr(), Fn.ld_of(pred), n, pred.shape[2], pred.shape[3], target.data_ptr(),
+            1 if chw else 0, th, tw, s.data_ptr(), s.data_ptr() + 16, _stream()), 'emsa_normal_angular_error')
+
+    def reset(self):
+        if self._state is not None:
+            self._state.zero_()
+
+    def counts(self):
+        """host copy of the state -> (error sum in units of 2^-20 rad, compared pixels); raises like
+        `compute()`"""
+        if self._state is None:
+            return 0, 0
+        s = self._state.cpu()
+        if int(s[2:].view(torch.int32)[0]):
+            raise ValueError("MeanAbsoluteNormalError: a predicted normal was not finite (the pixel was not "
+                             "compared)")
+        return int(s[0]), int(s[1])
+
+    def compute(self):
+        total, n = self.counts()
+        if n == 0:
+            return {'mae_rad': float('nan'), 'mae_deg': float('nan')}
+        rad = total / NORMAL_ANGLE_ONE / n
         return {'mae_rad': rad, 'mae_deg': math.degrees(rad)}
 
 

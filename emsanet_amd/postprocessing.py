@@ -471,6 +471,65 @@ class PanopticPostprocessing:
 
 
 # ---------------------------------------------------------------------------------------------
+# surface normals
+# ---------------------------------------------------------------------------------------------
+def normal_map(t, who, what, hw=None):
+    """a ground-truth normal map, checked -> (tensor whose memory the kernels read, chw flag, (N, H, W)).
+    float32 on the GPU, (N,H,W,3) as a loader yields it or (N,3,H,W) -- contiguous planes or a
+    channels-last view of (N,H,W,3) memory; with `hw` the map must have that size.  TypeError for another
+    type, NotImplementedError for a CPU tensor, ValueError for another shape or layout.
+    A limit, not resolved here: a contiguous tensor whose shape fits both readings -- (N,3,H,3) without
+    `hw`, (N,3,3,3) with `hw = (3, 3)` -- carries nothing that tells them apart.  Without `hw` it is read as
+    HWC, the loader's layout; with `hw` as CHW planes.  A caller with maps that small (the /32 scale of a
+    96 x 96 input) passes the channels-last (N,3,H,W) view, which is unambiguous."""
+    if not torch.is_tensor(t):
+        raise TypeError(f"{who}: {what} must be a tensor")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{who}: {what} has dtype {t.dtype}; float32 normal maps only")
+    hwc = t.dim() == 4 and t.shape[3] == 3 and (hw is None or tuple(t.shape[1:3]) == tuple(hw))
+    chw = t.dim() == 4 and t.shape[1] == 3 and (hw is None or tuple(t.shape[2:]) == tuple(hw))
+    if hw is not None and chw and hwc:
+        hwc = False                      # (H = W = 3: both readings fit, see the docstring)
+    if not (hwc or chw):
+        raise ValueError(f"{who}: {what} has shape {tuple(t.shape)}; expected (N, H, W, 3) or (N, 3, H, W)"
+                         + (f" with H x W = {hw[0]} x {hw[1]}" if hw is not None else ""))
+    if not t.is_cuda:
+        raise NotImplementedError(f"{who}: {what} is a CPU tensor; the normal task runs on the GPU only")
+    if hwc:
+        if not t.is_contiguous():
+            raise ValueError(f"{who}: {what} must be contiguous")
+        return t, False, tuple(t.shape[:3])
+    shape = (t.shape[0], t.shape[2], t.shape[3])
+    if t.permute(0, 2, 3, 1).is_contiguous():
+        return t, False, shape               # channels-last view: (N,H,W,3) memory
+    if t.is_contiguous():
+        return t, True, shape
+    raise ValueError(f"{who}: {what} must be contiguous (N, 3, H, W) planes or a channels-last view")
+
+
+class NormalPostprocessing:
+    """[U] unit-length surface normals: `prediction['normal_vectors']` = v / max(|v|_2, 1e-12) per pixel
+    of the raw `prediction['normal_output']`, in fp32 -- the semantics of
+    `torch.nn.functional.normalize(dim=1)`; float32 (N,3,h,w) over dense NHWC memory.  A separate
+    object the caller applies to the model's merged dictionary (the decoder returns the raw maps only;
+    what the un-vendored library does at this point is undetermined).  One launch of `emsa_normal_unit`
+    on the current stream."""
+
+    def __call__(self, prediction):
+        x = prediction.get('normal_output') if isinstance(prediction, dict) else None
+        if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != 3:
+            raise _lib.EmsaError("NormalPostprocessing: prediction['normal_output'] must be the (N, 3, h, w) "
+                                 "output of the normal decoder")
+        x = Fn.as_act(_f32(x, 'NormalPostprocessing: normal_output'))
+        n, _, h, w = x.shape
+        out = Fn.act_empty(n, 3, h, w, x.device)
+        check(_lib.lib().emsa_normal_unit(Fn._p(x), Fn.ld_of(x), n * h * w, Fn._p(out), Fn._stream()),
+              'emsa_normal_unit')
+        prediction['normal_vectors'] = out
+        return prediction
+
+
+# ---------------------------------------------------------------------------------------------
 # full-resolution predictions
 # ---------------------------------------------------------------------------------------------
 _FULLRES_LABEL_KEYS = ('instance_segmentation_idx', 'instance_segmentation_gt_foreground',

@@ -36,21 +36,27 @@ rule is restated here:
                  use_orientation[semantic] & the angle is not NaN (preprocessing.py:206-213).  [U]
   semantic       (N,H_s,W_s) int64, the down-scaled label, unchanged by the stuff clearing.
   scene          passed through as int64.
+  normal         (N,3,H_s,W_s) float32 over (N,H_s,W_s,3) memory, from batch['normal'] -- float32
+                 (N,H,W,3) or (N,3,H,W), channel 0 the image-x component, (0,0,0) = invalid: the vector at
+                 (y, x) of scale s is the full-resolution vector at (y * s, x * s), copied bit for bit (the
+                 nearest rule of the label maps), so its validity is that of the sampled vector.  Nothing is
+                 interpolated or re-normalised.  One more launch (csrc/normal.hip).  [U]
 `center_mask` is not produced (the loss takes None).
 """
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import EmsaTargetScale, check
+from ._lib import EmsaNormalScale, EmsaTargetScale, check
 from .functional import _stream
-from .postprocessing import thing_table
+from .postprocessing import normal_map, thing_table
 
 _LABEL_DTYPES = {torch.int64: 0, torch.int32: 1, torch.uint8: 2, torch.int16: 3, torch.uint16: 4}   # EMSA_LABEL_*
 MAX_INSTANCES = 1024
 MAX_SIGMA = 16
 DEFAULT_SCALES = (1, 32, 16, 8)      # the order TrainingLosses documents: full, then /32, /16, /8
 N_LAUNCHES = 3
+N_NORMAL_LAUNCHES = 1                # on top, with the normal task
 
 
 def scale_sigma(sigma, scale):
@@ -83,8 +89,10 @@ class TrainingTargetGenerator:
     """`generate(batch)` -> the `targets` dictionary of `TrainingLosses.forward(outputs, targets)`.
 
     args: `tasks`, `instance_center_sigma`, `instance_offset_encoding`,
-    `semantic_no_multiscale_supervision`, `instance_no_multiscale_supervision` (with a switch set that
-    task gets its full-scale entry only).  is_thing / use_orientation: per class, indexed by the label
+    `semantic_no_multiscale_supervision`, `instance_no_multiscale_supervision`,
+    `normal_no_multiscale_supervision` (with a switch set that task gets its full-scale entry only).
+    With the 'normal' task and a batch that carries 'normal', `targets['normal']` is the list of the
+    down-scaled maps.  is_thing / use_orientation: per class, indexed by the label
     WITH void.  scales: the first is the full resolution, then the side outputs in the decoder's order.
     max_instances bounds the instance ids: [0, max_instances), at most 1024.  ring: the outputs and the
     workspace rotate over that many sets, so the targets of the previous ring - 1 calls stay valid.
@@ -101,6 +109,7 @@ class TrainingTargetGenerator:
         self.with_instance = 'instance' in tasks or 'orientation' in tasks
         self.with_orientation = 'orientation' in tasks
         self.with_scene = 'scene' in tasks
+        self.with_normal = 'normal' in tasks
         self.is_thing = tuple(bool(t) for t in is_thing)
         if use_orientation is None:
             use_orientation = [False] * len(self.is_thing)
@@ -136,6 +145,9 @@ class TrainingTargetGenerator:
                 raise ValueError(f"TrainingTargetGenerator: sigma_{s} = {sg} (instance_center_sigma = "
                                  f"{self.sigma}) outside [1, {MAX_SIGMA}]")
             self.plan.append((s, sg, sem, inst))
+        normal_ms = not getattr(args, 'normal_no_multiscale_supervision', False)
+        self.normal_scales = tuple(s for i, s in enumerate(self.scales) if i == 0 or normal_ms) \
+            if self.with_normal else ()
         self._tables = {}            # device -> (is_thing, use_orientation, gauss tables, flags)
         self._rings = {}             # (device, N, H, W) -> [next slot, slots]
         self._last = None
@@ -189,10 +201,19 @@ class TrainingTargetGenerator:
                         e.orientation = d['orientation'].data_ptr()
                         e.orientation_foreground = d['orientation_foreground'].data_ptr()
                     inst_out.append(d)
-            nbytes = L.emsa_targets_workspace_bytes(n, len(self.plan), self.max_instances)
+            nbytes = L.emsa_targets_workspace_bytes(n, len(self.plan), self.max_instances) if self.plan else 0
             slots.append({'desc': desc, 'semantic': sem_out, 'instance': inst_out,
                           'ws': torch.zeros(nbytes, device=device, dtype=torch.uint8),
                           'scene': torch.empty(n, device=device, dtype=torch.int64)})
+            if self.with_normal:
+                ndesc = (EmsaNormalScale * len(self.normal_scales))()
+                normal_out = []
+                for e, s in zip(ndesc, self.normal_scales):
+                    # (N,3,H_s,W_s) with channels-last strides, like 'offset'
+                    t = torch.empty((n, h // s, w // s, 3), device=device, dtype=torch.float32)
+                    e.scale, e.out = s, t.data_ptr()
+                    normal_out.append(t.permute(0, 3, 1, 2))
+                slots[-1].update(normal_desc=ndesc, normal=normal_out)
         r = self._rings[key] = [0, slots]
         return r
 
@@ -245,6 +266,13 @@ class TrainingTargetGenerator:
                                 tuple(scene.shape) != (n,)):
             raise NotImplementedError("TrainingTargetGenerator.generate: batch['scene'] must be an (N,) "
                                       "tensor on the GPU")
+        normal = None
+        if self.with_normal and batch.get('normal') is not None:
+            normal, normal_chw, shape = normal_map(batch['normal'], 'TrainingTargetGenerator.generate',
+                                                   "batch['normal']")
+            if shape != (n, h, w) or normal.device != device:
+                raise ValueError(f"TrainingTargetGenerator.generate: semantic {tuple(sem.shape)} vs "
+                                 f"normal {tuple(batch['normal'].shape)}")
         is_thing, use_orientation, gauss, flags = self._constants(device)
         ring = self._slots(device, n, h, w)
         slot = ring[1][ring[0]]
@@ -274,6 +302,11 @@ class TrainingTargetGenerator:
             out['semantic'] = list(slot['semantic'])
         if self.with_instance:
             out['instance'] = [dict(d) for d in slot['instance']]
+        if normal is not None:
+            check(_lib.lib().emsa_normal_targets(normal.data_ptr(), 1 if normal_chw else 0, n, h, w,
+                                                 slot['normal_desc'], len(self.normal_scales), _stream()),
+                  'emsa_normal_targets')
+            out['normal'] = list(slot['normal'])
         if self.with_scene:
             out['scene'] = slot['scene']
             out['scene'].copy_(scene)         # (a copy: the caller may refill its buffer)

@@ -681,6 +681,62 @@ int emsa_augment_orientations(const float* orientations, float* out, const int32
                               int32_t max_instances, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The surface-normal task (csrc/normal.hip): loss, targets, augmentation, unit-length post-processing
+ * and metric.  The reference's task code lives in the un-vendored nicr_mt_scene_analysis library: every
+ * rule is a restatement, stated in emsanet_amd/loss.py, targets.py, augment.py, postprocessing.py and
+ * metrics.py.  A ground-truth map is float [n][h][w][3] (chw == 0) or [n][3][h][w] (chw != 0); channel
+ * 0 is the image-x component; a pixel is valid iff its vector is not exactly (0, 0, 0).  A prediction
+ * is float NHWC with a pixel stride ld >= 3 whose first three channels are read (one 16-byte access
+ * where ld % 4 == 0 and the pointer is 16-byte aligned).  At most 2^31 / 3 pixels per call.
+ *   emsa_normal_l1_blocks      workgroups of the loss: `partial` holds 2 * blocks 4-byte words
+ *   emsa_normal_l1_fwd         out[0] = sum over valid pixels and 3 channels of |p - t| / (3 n_valid)
+ *                              (0 without a valid pixel), out[1] = n_valid.  hw = pixels per image.
+ *                              Per-workgroup partials in fixed slots, a fixed-order second stage with an
+ *                              fp64 sum and an integer count: bit-reproducible.  out[1] carries the
+ *                              count as fp32: exact up to 2^24 valid pixels (a 32 x 480 x 640 batch has
+ *                              9.8 M), rounded to 24 bits beyond, which moves the backward's divisor by
+ *                              at most 6e-8 relative; the loss itself divides by the exact count.
+ *   emsa_normal_l1_bwd         d_pred rows of ld_d >= 3 floats, EVERY element written: grad_out[0] *
+ *                              sign(p - t) / (3 n_valid) in the three channels of a valid pixel (sign(0)
+ *                              = 0), 0 elsewhere and in the padding.  sums = `out` of the forward.
+ *   emsa_normal_targets        every scale in one launch: the vector at (y, x) of scale s is the one at
+ *                              (y * s, x * s), copied bit for bit.  `scales` is a HOST array of n_scales
+ *                              <= EMSA_TARGETS_MAX_SCALES entries; out float [n][h/s][w/s][3], 16-byte
+ *                              aligned; h and w must be multiples of every scale.
+ *   emsa_augment_normal        the map of the table `params` of emsa_augment_apply: source hs x ws ->
+ *                              out float [n][h][w][3]; composed index and nearest rule of depth and the
+ *                              labels, values copied, channel 0 negated where the sample's flip is set.
+ *   emsa_normal_unit           out float [pixels][3] = v / max(|v|_2, 1e-12) in fp32.
+ *   emsa_normal_angular_error  per valid pixel of target (n, th, tw): angle = atan2(|p x t|, p . t) in
+ *                              fp32, p read from pred (n, h, w) at the nearest-neighbour source pixel
+ *                              floor(y * h / th) (float arithmetic, as emsa_nearest_fwd_t); acc[0] +=
+ *                              round(angle * EMSA_NORMAL_ANGLE_ONE), acc[1] += 1 (int64[2], integer
+ *                              atomics: independent of the launch geometry and of the order).  A
+ *                              non-finite angle is not compared and sets *flag (int32).  The quantum
+ *                              2^-20 rad adds at most 4.8e-7 rad per pixel and leaves room for more than
+ *                              10^12 pixels.
+ * ------------------------------------------------------------------------------------------ */
+#define EMSA_NORMAL_ANGLE_ONE 1048576 /* 2^20: fixed point of the angular-error sum, in 1 / rad */
+typedef struct EmsaNormalScale {
+  int32_t scale, reserved;
+  float* out;
+} EmsaNormalScale;
+int emsa_normal_l1_blocks(int64_t pixels);
+int emsa_normal_l1_fwd(const float* pred, int32_t ld, const float* target, int32_t target_chw, int64_t hw,
+                       int64_t pixels, float* partial, float* out, void* stream);
+int emsa_normal_l1_bwd(const float* pred, int32_t ld, const float* target, int32_t target_chw, int64_t hw,
+                       int64_t pixels, const float* sums, const float* grad_out, float* d_pred,
+                       int32_t ld_d, void* stream);
+int emsa_normal_targets(const float* normal, int32_t chw, int32_t n, int32_t h, int32_t w,
+                        const EmsaNormalScale* scales, int32_t n_scales, void* stream);
+int emsa_augment_normal(const float* normal, int32_t chw, const int32_t* params, int32_t n, int32_t hs,
+                        int32_t ws, int32_t h, int32_t w, float* out, void* stream);
+int emsa_normal_unit(const float* pred, int32_t ld, int64_t pixels, float* out, void* stream);
+int emsa_normal_angular_error(const float* pred, int32_t ld, int32_t n, int32_t h, int32_t w,
+                              const float* target, int32_t target_chw, int32_t th, int32_t tw,
+                              int64_t* acc, int32_t* flag, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Optimizer step over one flat bucket: torch.optim.SGD(momentum, weight_decay,
  * nesterov=True) as the reference configures it (emsanet/optimizer.py:29-36), one pass:
  *   d = grad * grad_scale + weight_decay * p;  buf = first_step ? d : momentum * buf + d;
