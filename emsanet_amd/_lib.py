@@ -105,6 +105,11 @@ SIGNATURES = {
                                         POINTER(c_void_p), POINTER(c_void_p), _P, _P]),
     'emsa_pack_wino': (c_int, [_P, _P, _P, c_int32, c_int32, c_int32, _P]),
     'emsa_pack_batch': (c_int, [_P, c_int32, c_int32, _P]),
+    'emsa_conv_wino2d_supported': (c_int, [_GP]),
+    'emsa_conv_wino2d_stats_rows': (c_int, [_GP]),
+    'emsa_conv_wino2d': (c_int, [_GP, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, _P, c_int32, c_int32, _P]),
+    'emsa_pack_wino2d': (c_int, [_P, _P, _P, c_int32, c_int32, _P]),
+    'emsa_pack_wino2d_packed': (c_int, [_P, _P, c_int32, c_int32, c_int32, _P]),
     'emsa_pack_wino_packed': (c_int, [_P, _P, c_int32, c_int32, c_int32, c_int32, _P]),
     'emsa_conv_wgrad_ws_bytes': (c_int64, [_GP]),
     'emsa_conv_wgrad': (c_int, [_GP, _P, _P, _P, _P, _P, _P]),
@@ -285,6 +290,7 @@ SIGNATURES = {
     'emsa_prof_read_bytes': (c_int, [c_int32, POINTER(ctypes.c_double)]),
 }
 
+E_SHAPE = -1                 # EMSA_E_SHAPE: refused on the host, nothing was launched
 _ERR = {-1: 'EMSA_E_SHAPE (unsupported geometry)', -2: 'EMSA_E_ARG (bad argument)',
         -3: 'EMSA_E_LAUNCH (HIP launch failed)'}
 

@@ -33,6 +33,36 @@ __device__ __forceinline__ void emsa_st4(float* p, float4 v) {
 }
 __device__ __forceinline__ float4 emsa_zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 
+// U2 in memory: [16 comps][K steps of 8][n][8], so that the rows a workgroup fetches for one K step
+// are contiguous; the tail of a k_ch that is no multiple of 8 is padding the kernel never reads.
+__host__ __device__ __forceinline__ size_t emsa_wino2d_at(int comp, int n, int k, int n_ch, int k_ch) {
+  return ((((size_t)comp * ((k_ch + 7) >> 3) + (k >> 3)) * n_ch + n) << 3) + (k & 7);
+}
+// component of the flipped kernel (data gradient): 0 <-> 3 in both directions
+__host__ __device__ __forceinline__ int emsa_wino2d_flip(int comp) {
+  const int i = comp >> 2, j = comp & 3;
+  return (i == 0 ? 3 : i == 3 ? 0 : i) * 4 + (j == 0 ? 3 : j == 3 ? 0 : j);
+}
+// Winograd F(2x2,3x3) weight transform U2 = G g G^T of one 3x3 kernel g[r][t]: component
+// i*4 + j = (row transform i, column transform j), G = (g0, (g0+g1+g2)/2, (g0-g1+g2)/2, g2).  First
+// along the kernel row (the row-Winograd U of emsa_pack_wino), then the same transform across the
+// three rows.  Every route to U2 goes through this one function; the halvings are exact and the sums
+// commutative, so the transform of the flipped kernel is this one with components 0 <-> 3 swapped
+// in both directions, bit for bit.
+__device__ __forceinline__ void emsa_wino2d_u(const float g[9], float u[16]) {
+  float t[3][4];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const float s = 0.5f * (g[r * 3] + g[r * 3 + 2]), h = 0.5f * g[r * 3 + 1];
+    t[r][0] = g[r * 3]; t[r][1] = s + h; t[r][2] = s - h; t[r][3] = g[r * 3 + 2];
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float s = 0.5f * (t[0][j] + t[2][j]), h = 0.5f * t[1][j];
+    u[j] = t[0][j]; u[4 + j] = s + h; u[8 + j] = s - h; u[12 + j] = t[2][j];
+  }
+}
+
 // ---- 16-bit activation storage (BASELINE configs 3 / 5: bf16 training, fp16|bf16 inference) ------
 // Kernels templated on the STORAGE type T of their activation tensors read / write through these
 // overloads; all arithmetic stays fp32 in registers.  Four consecutive channels = one 8-byte access

@@ -636,6 +636,8 @@ __global__ void pack_wino_packed_kernel(const float* __restrict__ wp, float* __r
 // layouts (dst0 = [tap][cout][cin], dst1 = [tap][cin][cout]); kind 1: OIHW -> Winograd U
 // (dst0 forward, dst1 data gradient; rows = 3 for a 3x3 kernel); NULL outputs are skipped
 // kind 2 / 3: as kind 0 with bf16 / fp16 outputs (operands of conv_h.hip)
+// kind 7: OIHW 3x3 -> the F(2x2,3x3) weights U2 of conv_wino2d.hip (dst0 forward, dst1
+// data gradient), the transform of emsa_pack_wino2d
 // kind 5 / 6: as 2 / 3 in the fragment order of conv_rs.hip (channel counts multiples of 32)
 // kind 5 / 6: bf16 / fp16 in the MFMA-fragment order of conv_rs.hip (emsa_pack_weight_frag_t):
 // element (tap r, row n, column k) of an [r][nT][kT] operand lives at
@@ -679,10 +681,52 @@ __global__ __launch_bounds__(256) void pack_batch_kernel(const EmsaPackJob* __re
   const int tco = (cout + 31) / 32, tci = (cin + 31) / 32;
   const bool wino = jb.kind == 1;
   const int taps = jb.kh * jb.kw;
-  const int R = wino ? ((jb.kh == 3 && jb.kw == 3) ? 3 : 1) : taps;   // slices per (co, ci)
+  const bool wino2 = jb.kind == 7;       // 3x3 only: one slice carries all nine taps
+  const int R = wino ? ((jb.kh == 3 && jb.kw == 3) ? 3 : 1) : (wino2 ? 1 : taps);   // slices per (co, ci)
   const int n_tiles = tco * tci * R;
   for (int tile = blockIdx.x - jb.first_block; tile < n_tiles; tile += nblk) {
     const int r = tile % R, t2 = tile / R, ci0 = (t2 % tci) * 32, co0 = (t2 / tci) * 32;
+    if (wino2) {
+      float v2[4][16];                     // [row group k][component i*4 + j]
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int co = co0 + ty + 8 * k, ci = ci0 + tx;
+        const bool ok = co < cout && ci < cin;
+        float g[9];
+#pragma unroll
+        for (int t = 0; t < 9; ++t) g[t] = ok ? jb.src[((size_t)co * cin + ci) * 9 + t] : 0.f;
+        emsa_wino2d_u(g, v2[k]);
+        if (ok && jb.dst0) {
+#pragma unroll
+          for (int c = 0; c < 16; ++c)
+            jb.dst0[emsa_wino2d_at(c, co + coO, ci + ciO, coT, ciT)] = v2[k][c];
+        }
+      }
+      if (jb.dst1) {
+        // data gradient: channels transposed through LDS, four components (one row component i)
+        // per pass; kernel flipped in both directions = components 0 <-> 3 swapped
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          __syncthreads();
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) tr[j][ty + 8 * k][tx] = v2[k][i * 4 + j];
+          __syncthreads();
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const int ci = ci0 + ty + 8 * k, co = co0 + tx;
+            if (ci < cin && co < cout) {
+#pragma unroll
+              for (int j = 0; j < 4; ++j)
+                jb.dst1[emsa_wino2d_at(emsa_wino2d_flip(i * 4 + j), ci + ciO, co + coO, ciT, coT)] =
+                    tr[j][tx][ty + 8 * k];
+            }
+          }
+        }
+      }
+      continue;
+    }
     float vals[4][4];                      // [row group k][component]
 #pragma unroll
     for (int k = 0; k < 4; ++k) {

@@ -354,8 +354,77 @@ def pack_wino_packed(wp, n_ch, k_ch, rows, flip):
     return u
 
 
+# The dense 3x3 convs as 2-D Winograd F(2x2,3x3) (conv_wino2d.hip) instead of the row form: read
+# once from EMSA_WINO2D (0 / 1 forces it off / on for every eligible shape).
+_WINO2D_ENV = os.environ.get('EMSA_WINO2D')
+WINO2D = None                # tests: True / False overrides the per-shape rule
+# per-shape rule (cin, cout) -> 2-D form, from profiles/wino2d_conv_bench.txt: the shapes it measured
+# faster on than the row kernel, forward and data gradient both.  512->512 at /32 (0.82-0.92x) stays
+# on the row kernel; 96->8 was not measured and stays there too.
+WINO2D_SHAPES = frozenset({(512, 256), (256, 128), (128, 40), (128, 96)})
+
+
+# calls that were handed U2 and ran on the row kernel all the same (geometry or operand
+# combination the 2-D kernel refuses): 0 in the model's training and inference steps -- a caller
+# that starts to fall back shows here instead of silently losing the faster kernel
+WINO2D_FALLBACKS = 0
+
+
+def _wino2d_fell_back():
+    global WINO2D_FALLBACKS
+    WINO2D_FALLBACKS += 1
+
+
+def wino2d_eligible(spec):
+    return (spec.kh, spec.kw, spec.ph, spec.pw) == (3, 3, 1, 1) and wino_eligible(spec)
+
+
+def wino2d_selected(spec):
+    """this 3x3 conv runs (and packs its weights for) the 2-D Winograd kernel"""
+    if not wino2d_eligible(spec):
+        return False
+    if WINO2D is not None:
+        return bool(WINO2D)
+    if _WINO2D_ENV is not None:
+        return _WINO2D_ENV != '0'
+    return (spec.cin, spec.cout) in WINO2D_SHAPES
+
+
+def wino2d_numel(n_ch, k_ch):
+    """floats of U2 = [16][ceil(k/8)][n][8] (the K steps of a row contiguous)"""
+    return 16 * n_ch * 8 * ((k_ch + 7) // 8)
+
+
+def _wino2d_buf(n_ch, k_ch, dev):
+    # the padding of a k_ch that is no multiple of 8 is never read by the kernel; zero, so that
+    # two packs of the same weights compare equal
+    n = wino2d_numel(n_ch, k_ch)
+    return _empty((n,), dev) if k_ch % 8 == 0 else torch.zeros(n, device=dev, dtype=torch.float32)
+
+
+def pack_wino2d(w, fwd=True, dgrad=False):
+    """OIHW [cout][cin][3][3] -> F(2x2,3x3) weights U2 [16][k/8][n][8]: forward (n,k = cout,cin) and/or
+    data gradient (n,k = cin,cout, flipped kernel), one launch.  -> (u or None, ud or None)"""
+    cout, cin, kh, kw = w.shape
+    u = _wino2d_buf(cout, cin, w.device) if fwd else None
+    ud = _wino2d_buf(cin, cout, w.device) if dgrad else None
+    check(_lib.lib().emsa_pack_wino2d(_p(w.contiguous()), _p(u), _p(ud), cout, cin, _stream()),
+          'emsa_pack_wino2d')
+    return u, ud
+
+
+def pack_wino2d_packed(wp, n_ch, k_ch, flip):
+    """U2 from a PACKED [tap][n_ch][k_ch] 3x3 weight (merged / channel-padded convs); flip=True for
+    a data-gradient pack [tap][cin][cout]"""
+    u = _wino2d_buf(n_ch, k_ch, wp.device)
+    check(_lib.lib().emsa_pack_wino2d_packed(_p(wp), _p(u), n_ch, k_ch, 1 if flip else 0,
+                                             _stream()), 'emsa_pack_wino2d_packed')
+    return u
+
+
 def conv_fwd(x, wp, spec, bias=None, want_stats=False, scale=None, shift=None, residual=None,
-             act=ACT_NONE, out=None, wino_u=None, want_relu_bits=False, in_affine=None, wfrag=None):
+             act=ACT_NONE, out=None, wino_u=None, want_relu_bits=False, in_affine=None, wfrag=None,
+             wino2d_u=None):
     """wp = packed [tap][cout][cin] weights in the dtype of `x` (MFMA implicit GEMM) -- or, fp32
     only, wino_u = Winograd weights of an eligible conv (emsa_conv1d_wino).  want_relu_bits
     (Winograd kernel with act = ReLU): additionally returns (out > 0) as a bit mask for
@@ -363,7 +432,10 @@ def conv_fwd(x, wp, spec, bias=None, want_stats=False, scale=None, shift=None, r
     conv runs on relu(x * scale + shift) formed in its loader (emsa_conv1d_wino_inbn: the
     BatchNorm + ReLU in front of a 1-D Winograd conv without a pass of its own).  wfrag = the
     fragment-ordered 16-bit weights of a 3-tap 1-D conv: where emsa_conv1d_rs_t takes the geometry
-    it runs instead of the implicit GEMM (same epilogue, its own statistics rows)."""
+    it runs instead of the implicit GEMM (same epilogue, its own statistics rows).  wino2d_u = the
+    F(2x2,3x3) weights of a dense 3x3 conv (emsa_conv_wino2d); where that kernel refuses the
+    geometry or the operand combination (EMSA_E_SHAPE, before any launch) the call goes on with
+    `wino_u`, which may be a callable that packs on demand."""
     n, c, h, w = x.shape
     oh, ow = spec.out_hw(h, w)
     code = dt(x)
@@ -372,6 +444,26 @@ def conv_fwd(x, wp, spec, bias=None, want_stats=False, scale=None, shift=None, r
     g = spec.geom_fwd(n, h, w, ld_of(x), ld_of(out))
     L = _lib.lib()
     stats = None
+    if wino2d_u is not None and code == 0:
+        # asked before anything is allocated: the geometry, and the kernel's operand rule
+        # (statistics are those of the conv's own result + bias; no bit masks, no folded input)
+        takes = not want_relu_bits and in_affine is None and \
+            not (want_stats and (scale is not None or residual is not None or act != ACT_NONE)) and \
+            L.emsa_conv_wino2d_supported(g) == 1
+        if takes:
+            if want_stats:
+                stats = _empty((3, L.emsa_conv_wino2d_stats_rows(g), spec.cout), x.device)
+            rc = L.emsa_conv_wino2d(g, _p(x), _p(wino2d_u), _p(out), _p(bias), _p(stats), _p(scale),
+                                    _p(shift), _p(residual),
+                                    ld_of(residual) if residual is not None else 0, None, 0, act,
+                                    _stream())
+            if rc == 0:
+                return (out, stats) if want_stats else out
+            if rc != _lib.E_SHAPE:               # (E_SHAPE here: an operand's alignment)
+                check(rc, 'emsa_conv_wino2d')
+            stats = None
+        _wino2d_fell_back()
+    wino_u = _resolve(wino_u)
     if code != 0:
         wino_u = None                       # the 16-bit path is conv_rs.hip / conv_h.hip
     use_rs = wfrag is not None and wfrag.dtype == x.dtype and rs_supported(code, g) and \
@@ -636,9 +728,10 @@ def _conv_dgrad_phased(dy, wpd, spec, in_hw, mask_src, residual, out):
 
 
 def conv_dgrad(dy, wpd, spec, in_hw, mask_src=None, residual=None, out=None, wino_u=None,
-               mask_bits=None, wfrag=None):
+               mask_bits=None, wfrag=None, wino2d_u=None):
     """dx = conv_transpose(dy); optional fused `* (mask_src > 0)` -- or the same mask as bits
-    (`mask_bits`, Winograd kernel only) -- and `+ residual`."""
+    (`mask_bits`, Winograd kernel only) -- and `+ residual`.  wino2d_u = the F(2x2,3x3)
+    data-gradient weights of a dense 3x3 conv; falls back to `wino_u` as conv_fwd does."""
     n = dy.shape[0]
     h, w = in_hw
     code = dt(dy)
@@ -647,6 +740,18 @@ def conv_dgrad(dy, wpd, spec, in_hw, mask_src=None, residual=None, out=None, win
     g = spec.geom_dgrad(n, h, w, ld_of(dy), ld_of(out))
     L = _lib.lib()
     lr = ld_of(residual) if residual is not None else 0
+    if wino2d_u is not None and code == 0:
+        if mask_bits is None and L.emsa_conv_wino2d_supported(g) == 1:
+            rc = L.emsa_conv_wino2d(g, _p(dy), _p(wino2d_u), _p(out), None, None, None, None,
+                                    _p(residual), lr, _p(mask_src),
+                                    ld_of(mask_src) if mask_src is not None else 0, ACT_NONE,
+                                    _stream())
+            if rc == 0:
+                return out
+            if rc != _lib.E_SHAPE:
+                check(rc, 'emsa_conv_wino2d(dgrad)')
+        _wino2d_fell_back()
+    wino_u = _resolve(wino_u)
     if code != 0:
         wino_u = None
     if wino_u is None and (spec.sh > 1 or spec.sw > 1):

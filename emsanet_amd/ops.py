@@ -86,6 +86,12 @@ class ConvRT:
         self._keyu = None
         self._u = None
         self._ud = None
+        # dense 3x3 convs the per-shape rule sends to the 2-D Winograd F(2x2,3x3) kernel hold its
+        # weights U2 as well; the row form stays (fallback for what that kernel refuses)
+        self.wino2d = self.wino and Fn.wino2d_selected(self.spec)
+        self._keyu2 = None
+        self._u2 = None
+        self._ud2 = None
         self._h = {}              # 16-bit packs: dtype -> [key, fwd, key_d, dgrad]
         # stride-1 3x1 / 1x3 convs with 64..512 channels in 16-bit storage: the register-stationary
         # streaming kernel (conv_rs.hip) with fragment-ordered weights, where it takes the geometry
@@ -105,11 +111,22 @@ class ConvRT:
             self._keyu = key
         return self._u, self._ud
 
+    def _wino2d_weights(self):
+        w = self.conv.weight
+        key = (w._version, w.data_ptr())
+        if key != self._keyu2:
+            self._u2, self._ud2 = Fn.pack_wino2d(w.detach(), fwd=True, dgrad=w.requires_grad)
+            self._keyu2 = key
+        return self._u2, self._ud2
+
     def forward(self, x, **kw):
         """conv forward through the best kernel for this layer (fused-epilogue kwargs of conv_fwd)"""
         if x.dtype != torch.float32:
             wf = self.frag(x.dtype)
             return Fn.conv_fwd(x, self._plain(x.dtype, wf, self.packed), self.spec, wfrag=wf, **kw)
+        if self.wino2d:
+            return Fn.conv_fwd(x, None, self.spec, wino2d_u=self._wino2d_weights()[0],
+                               wino_u=lambda: self._wino_weights()[0], **kw)
         if self.wino:
             return Fn.conv_fwd(x, None, self.spec, wino_u=self._wino_weights()[0], **kw)
         return Fn.conv_fwd(x, self.packed(), self.spec, **kw)
@@ -129,12 +146,22 @@ class ConvRT:
             wf = self.frag_dgrad(dy.dtype)
             return Fn.conv_dgrad(dy, self._plain(dy.dtype, wf, self.packed_dgrad), self.spec, in_hw,
                                  wfrag=wf, **kw)
+        if self.wino2d and mask_bits is None:
+            ud2 = self._wino2d_weights()[1]
+            if ud2 is None:
+                ud2 = Fn.pack_wino2d(self.conv.weight.detach(), fwd=False, dgrad=True)[1]
+            return Fn.conv_dgrad(dy, None, self.spec, in_hw, wino2d_u=ud2,
+                                 wino_u=self._row_dgrad_weights, **kw)
         if self.wino:
-            u, ud = self._wino_weights()
-            if ud is None:
-                ud = Fn.pack_wino(self.conv.weight.detach(), fwd=False, dgrad=True)[1]
-            return Fn.conv_dgrad(dy, None, self.spec, in_hw, wino_u=ud, mask_bits=mask_bits, **kw)
+            return Fn.conv_dgrad(dy, None, self.spec, in_hw, wino_u=self._row_dgrad_weights(),
+                                 mask_bits=mask_bits, **kw)
         return Fn.conv_dgrad(dy, self.packed_dgrad(), self.spec, in_hw, **kw)
+
+    def _row_dgrad_weights(self):
+        ud = self._wino_weights()[1]
+        if ud is None:
+            ud = Fn.pack_wino(self.conv.weight.detach(), fwd=False, dgrad=True)[1]
+        return ud
 
     def dgrad_bnb(self, dy, in_hw, t, affine, mean, invstd, residual=None, force=False):
         """data gradient + the backward reduction of the BatchNorm in front of this conv
@@ -283,7 +310,8 @@ class PackPlan:
 
     def _build(self, dev, dtype, lean=False):
         if self._captured and self._jobs is not None:
-            self._retired.append((self._jobs, self._arena, self._views, self._frag, self._mviews))
+            self._retired.append((self._jobs, self._arena, self._views, self._frag, self._mviews,
+                                  self._w2))
         self._lean = lean
         n = len(self.rts)
         n_multi = sum(len(m.placements) + sum(1 for q, _, _ in m.placements if q.bias is not None)
@@ -294,7 +322,10 @@ class PackPlan:
         frag_rts = [rt for rt in self.rts if half and rt.rs and Fn.CONV_RS]
         lean = self._lean = bool(lean and frag_rts)
         skip = set(id(rt) for rt in frag_rts) if lean else set()
-        jobs = (_lib.EmsaPackJob * (n + n_multi + len(frag_rts)))()
+        # the dense 3x3 convs on the 2-D Winograd kernel get U2 (pack kind 7) BESIDE their row form
+        w2_rts = [rt for rt in self.rts if not half and rt.wino2d]
+        n_multi2 = sum(len(m.placements) for m in self.multi if m.wino2d and not half)
+        jobs = (_lib.EmsaPackJob * (n + n_multi + len(frag_rts) + len(w2_rts) + n_multi2))()
         esz = 2 if half else 4
         sizes = []
         for rt in self.rts:
@@ -308,7 +339,13 @@ class PackPlan:
                 sizes.append((per, per_b, per_b if w.requires_grad else 0))
         fsizes = [((rt.conv.weight.numel() * esz + 15) // 16 * 16) * (2 if rt.conv.weight.requires_grad else 1)
                   for rt in frag_rts]
-        arena = torch.empty(sum(a + b for _, a, b in sizes) + sum(fsizes), device=dev,
+        # (U2 forward and data gradient have the same size when both channel counts are multiples of
+        # 8, which the per-shape rule's convs are; otherwise the larger of the two)
+        w2numel = [max(Fn.wino2d_numel(rt.spec.cout, rt.spec.cin),
+                       Fn.wino2d_numel(rt.spec.cin, rt.spec.cout)) for rt in w2_rts]
+        w2sizes = [nel * 4 * (2 if rt.conv.weight.requires_grad else 1)
+                   for rt, nel in zip(w2_rts, w2numel)]
+        arena = torch.empty(sum(a + b for _, a, b in sizes) + sum(fsizes) + sum(w2sizes), device=dev,
                             dtype=torch.uint8)
         views, off, blk = [], 0, 0
         for j, (rt, (per, a, b)) in enumerate(zip(self.rts, sizes)):
@@ -345,6 +382,24 @@ class PackPlan:
             blk += max(1, min(64, (w.numel() + 2047) // 2048))
             j += 1
         self._frag = (frag_rts, fviews)
+        w2views = []
+        for rt, fs in zip(w2_rts, w2sizes):
+            w = rt.conv.weight
+            one = fs // 2 if w.requires_grad else fs
+            u0 = arena[off:off + 4 * Fn.wino2d_numel(rt.spec.cout, rt.spec.cin)].view(torch.float32)
+            u1 = arena[off + one:off + one + 4 * Fn.wino2d_numel(rt.spec.cin, rt.spec.cout)] \
+                .view(torch.float32) if w.requires_grad else None
+            if rt.spec.cin % 8 or rt.spec.cout % 8:
+                arena[off:off + fs].zero_()        # the K-step padding, never read by the kernel
+            off += fs
+            w2views.append((u0, u1))
+            cout, cin, kh, kw = w.shape
+            jobs[j] = _lib.EmsaPackJob(w.data_ptr(), u0.data_ptr(),
+                                       u1.data_ptr() if u1 is not None else None, cout, cin, kh, kw,
+                                       7, blk)
+            blk += max(1, min(64, (w.numel() + 2047) // 2048))
+            j += 1
+        self._w2 = (w2_rts, w2views)
         mviews = []
         for m in self.multi:
             sp = m.spec
@@ -368,7 +423,18 @@ class PackPlan:
                                                q.bias.shape[0], 1, 1, 1, 4, blk, sp.cout, co, 1, 0)
                     blk += 1
                     j += 1
-            mviews.append((d0, d1, bias, wino))
+            d2 = d3 = None
+            if wino and m.wino2d:
+                d2 = torch.zeros(Fn.wino2d_numel(sp.cout, sp.cin), device=dev, dtype=dtype)   # U2 forward
+                d3 = torch.zeros(Fn.wino2d_numel(sp.cin, sp.cout), device=dev, dtype=dtype)   # data gradient
+                for q, co, ci in m.placements:
+                    w4 = m._w4(q)
+                    cout, cin, kh, kw = w4.shape
+                    jobs[j] = _lib.EmsaPackJob(q.weight.data_ptr(), d2.data_ptr(), d3.data_ptr(), cout,
+                                               cin, kh, kw, 7, blk, sp.cout, co, sp.cin, ci)
+                    blk += max(1, min(64, (w4.numel() + 2047) // 2048))
+                    j += 1
+            mviews.append((d0, d1, bias, wino, d2, d3))
         self._mviews = mviews
         self._n_jobs = j
         raw = torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8).to(dev)
@@ -407,7 +473,9 @@ class PackPlan:
         self._asked_seen = asked
         check(_lib.lib().emsa_pack_batch(self._jobs.data_ptr(), self._n_jobs, self._n_blocks,
                                          Fn._stream()), 'emsa_pack_batch')
-        for m, mk, (d0, d1, bias, wino) in zip(self.multi, mkeys, self._mviews):
+        for m, mk, (d0, d1, bias, wino, d2, d3) in zip(self.multi, mkeys, self._mviews):
+            if d2 is not None:
+                m._u2, m._ud2, m._key2 = d2, d3, mk
             if dtype != torch.float32:
                 m._h[dtype] = (mk, d0, bias)
                 m._hd[dtype] = (mk, d1, None)
@@ -421,6 +489,9 @@ class PackPlan:
             w = rt.conv.weight
             k = (w._version, w.data_ptr())
             rt._hf[dtype] = [k, f0, k if f1 is not None else None, f1]
+        for rt, (u0, u1) in zip(*self._w2):
+            w = rt.conv.weight
+            rt._u2, rt._ud2, rt._keyu2 = u0, u1, (w._version, w.data_ptr())
         for rt, (v0, v1), w in zip(self.rts, self._views, ws):
             k = (w._version, w.data_ptr())
             if v0 is None:
@@ -1059,6 +1130,30 @@ class MultiConvRT:
         self.has_bias = any(m.bias is not None for m, _, _ in placements)
         # 3x3 stride-1 merged convs (the task heads) run on the Winograd kernel as well
         self.wino = Fn.wino_eligible(self.spec) and os.environ.get('EMSA_WINO', '1') != '0'
+        # merged 3x3 heads the per-shape rule sends to the 2-D Winograd kernel: U2 beside the row form
+        self.wino2d = self.wino and Fn.wino2d_selected(self.spec)
+        self._key2 = None
+        self._u2 = None              # forward U2
+        self._ud2 = None             # data-gradient U2 (same key)
+
+    def _wino2d_weights(self):
+        """(forward, data-gradient) U2 of the assembled operand: PackPlan's when fresh, else re-packed"""
+        key = self._key_now()
+        if key != self._key2:
+            s = self.spec
+            self._u2 = Fn.pack_wino2d_packed(self._packed_fwd(),
+                                             s.cout, s.cin, flip=False)
+            self._ud2 = Fn.pack_wino2d_packed(self.packed_dgrad(), s.cin, s.cout, flip=True)
+            self._key2 = key
+        return self._u2, self._ud2
+
+    def _packed_fwd(self):
+        s = self.spec
+        wp = torch.zeros(s.kh * s.kw * s.cout * s.cin, device=self.placements[0][0].weight.device,
+                         dtype=torch.float32)
+        for m, co, ci in self.placements:
+            Fn.pack_weight(self._w4(m).detach(), 'fwd', s.cout, co, s.cin, ci, out=wp)
+        return wp
 
     def _w4(self, m):
         w = m.weight
@@ -1110,6 +1205,9 @@ class MultiConvRT:
             wp, bias = self.packed_t(x.dtype)
             return Fn.conv_fwd(x, wp, self.spec, bias=bias)
         wp, bias = self.packed()
+        if self.wino2d:
+            return Fn.conv_fwd(x, None, self.spec, bias=bias, wino_u=self._u,
+                               wino2d_u=self._wino2d_weights()[0])
         if self.wino:
             return Fn.conv_fwd(x, None, self.spec, bias=bias, wino_u=self._u)
         return Fn.conv_fwd(x, wp, self.spec, bias=bias)
@@ -1134,6 +1232,9 @@ class MultiConvRT:
             ent = (key, wpd, ud)
             self._hd[dy.dtype] = ent
         _, wpd, ud = ent
+        if ud is not None and self.wino2d:
+            return Fn.conv_dgrad(dy, None, self.spec, in_hw, wino_u=ud,
+                                 wino2d_u=self._wino2d_weights()[1])
         if ud is not None:
             return Fn.conv_dgrad(dy, None, self.spec, in_hw, wino_u=ud)
         return Fn.conv_dgrad(dy, wpd, self.spec, in_hw)

@@ -179,10 +179,32 @@ int emsa_pack_wino(const float* w_oihw, float* u, float* u_dgrad, int32_t cout, 
                    int32_t rows, void* stream);
 int emsa_pack_wino_packed(const float* w_packed, float* u, int32_t n_ch, int32_t k_ch,
                           int32_t rows, int32_t flip, void* stream);
+/* 2-D Winograd F(2x2,3x3) variant for the dense stride-1 "same" 3x3 convs (forward and data
+ * gradient): 16 GEMMs over a quarter of the pixels, 16 of the 36 direct multiplies per 2x2 output
+ * tile where the row form above runs 24.  u2 = transformed weights [16][ceil(k_ch/8)][n_ch][8]
+ * (the channels of one K step of a row contiguous; 16 * n_ch * 8 * ceil(k_ch/8) floats), component
+ * i*4 + j = (kernel-row transform i, kernel-column transform j) of G g G^T, from emsa_pack_wino2d
+ * (OIHW parameter; u_dgrad: kernel flipped, channels transposed), emsa_pack_wino2d_packed (packed
+ * [tap][n][k] layout, flip = 1 for a data-gradient pack) or emsa_pack_batch kind 7; all three give
+ * the same bits.  Arguments and epilogue as emsa_conv_igemm; statistics rows (the same
+ * [3][rows][n_ch] layout) = emsa_conv_wino2d_stats_rows(g).  EMSA_E_SHAPE, before any launch, for
+ * a geometry emsa_conv_wino2d_supported refuses and for statistics combined with scale / shift,
+ * residual, mask_src or an activation.                                                          */
+int emsa_conv_wino2d_supported(const EmsaConvGeom* g);
+int emsa_conv_wino2d_stats_rows(const EmsaConvGeom* g);
+int emsa_conv_wino2d(const EmsaConvGeom* g, const float* in, const float* u2, float* out,
+                     const float* bias, float* stats, const float* scale, const float* shift,
+                     const float* residual, int32_t ld_res, const float* mask_src,
+                     int32_t ld_mask, int32_t act, void* stream);
+int emsa_pack_wino2d(const float* w_oihw, float* u, float* u_dgrad, int32_t cout, int32_t cin,
+                     void* stream);
+int emsa_pack_wino2d_packed(const float* w_packed, float* u, int32_t n_ch, int32_t k_ch,
+                            int32_t flip, void* stream);
 /* All weight transforms of a model in ONE launch: a table of jobs in DEVICE memory, job j owns the
  * workgroups [first_block_j, first_block_(j+1)) of a grid of total_blocks (first_block ascending
  * from 0).  kind 0: OIHW -> the packed layouts of emsa_pack_weight_pair (dst0 forward, dst1 data
- * gradient); kind 1: OIHW -> the Winograd weights of emsa_pack_wino (dst0 = u, dst1 = u_dgrad).
+ * gradient); kind 1: OIHW -> the Winograd weights of emsa_pack_wino (dst0 = u, dst1 = u_dgrad);
+ * kind 7: OIHW 3x3 -> the F(2x2,3x3) weights of emsa_pack_wino2d (dst0 = u, dst1 = u_dgrad).
  * NULL destinations are skipped.                                                                */
 typedef struct EmsaPackJob {
   const float* src;

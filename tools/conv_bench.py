@@ -1,5 +1,6 @@
 """Micro-benchmark of the MFMA convolution kernels on the layer shapes of the bs=32 640x480
-workload (GPU box).  usage: python tools/conv_bench.py [fwd|dgrad|wgrad|wino|all] [tile ...]
+workload (GPU box).  usage: python tools/conv_bench.py [fwd|dgrad|wgrad|wino|wino2d|all] [tile ...]
+(wino2d: the dense 3x3 convs, row-Winograd versus 2-D F(2x2,3x3) in the same run)
 EMSA_LIB selects an alternative build (ablations)."""
 import os
 import sys
@@ -19,8 +20,10 @@ SHAPES = [
     ('3x1 c256 /16', 256, 256, (3, 1), 1, (1, 0), 30, 40),
     ('1x3 c512 /32', 512, 512, (1, 3), 1, (0, 1), 15, 20),
     ('3x3 512->512 /32', 512, 512, (3, 3), 1, (1, 1), 15, 20),
+    ('3x3 512->256 /16', 512, 256, (3, 3), 1, (1, 1), 30, 40),
     ('3x3 256->128 /8', 256, 128, (3, 3), 1, (1, 1), 60, 80),
     ('3x3 128->40 /4', 128, 40, (3, 3), 1, (1, 1), 120, 160),
+    ('3x3 128->96 /4', 128, 96, (3, 3), 1, (1, 1), 120, 160),
     # memory-bound 1x1 convs (decoder skip connections) and a stride-2 block conv
     ('1x1 c64 /4', 64, 64, (1, 1), 1, (0, 0), 120, 160),
     ('1x1 c128 /8', 128, 128, (1, 1), 1, (0, 0), 60, 80),
@@ -54,6 +57,8 @@ def main():
         if only and only not in name:
             continue
         spec = Fn.ConvSpec(cin, cout, k, s, p)
+        if what == 'wino2d' and not Fn.wino2d_eligible(spec):
+            continue
         oh, ow = spec.out_hw(h, w)
         set_bytes = 4 * n * (2 * cin * h * w + 2 * cout * oh * ow)
         nb = 1 if os.environ.get('EMSA_BENCH_HOT') else max(2, -(-(768 << 20) // set_bytes))
@@ -93,6 +98,19 @@ def main():
             us = timeit(lambda i: Fn.conv_dgrad(DY[i % nb], None, spec, (h, w),
                                                 mask_src=X[i % nb], out=DX[i % nb], wino_u=ud))
             row += f" dgrad {us:7.1f}us {flops / us / 1e6:6.1f} |"
+        if what == 'wino2d' and Fn.wino2d_eligible(spec):
+            u, ud = Fn.pack_wino(wt, fwd=True, dgrad=True)
+            u2, ud2 = Fn.pack_wino2d(wt, fwd=True, dgrad=True)
+            for tag, kw in (('fwd', dict(bias=bias, act=1)), ('+stats', dict(want_stats=True))):
+                a = timeit(lambda i: Fn.conv_fwd(X[i % nb], None, spec, out=Y[i % nb], wino_u=u, **kw))
+                b = timeit(lambda i: Fn.conv_fwd(X[i % nb], None, spec, out=Y[i % nb], wino2d_u=u2,
+                                                 **kw))
+                row += f" {tag} row {a:7.1f}us 2d {b:7.1f}us x{a / b:4.2f} |"
+            a = timeit(lambda i: Fn.conv_dgrad(DY[i % nb], None, spec, (h, w), mask_src=X[i % nb],
+                                               out=DX[i % nb], wino_u=ud))
+            b = timeit(lambda i: Fn.conv_dgrad(DY[i % nb], None, spec, (h, w), mask_src=X[i % nb],
+                                               out=DX[i % nb], wino2d_u=ud2))
+            row += f" dgrad row {a:7.1f}us 2d {b:7.1f}us x{a / b:4.2f} |"
         if what in ('inbn', 'all') and Fn.wino_eligible(spec) and Fn.wino_rows(spec) == 1:
             # the NBt1D block's bn1 folded into the loaders (forward, weight gradient) and into the
             # data gradient's epilogue, next to the unfolded launches they replace
