@@ -250,6 +250,14 @@ SIGNATURES = {
     'emsa_channel_mean_t': (c_int, [c_int32, _P, _P, _P, c_int32, c_int64, c_int32, _P]),
     'emsa_se_pair_fwd_t': (c_int, [c_int32] + [_P] * 14 + [c_int32, c_int64, c_int32, c_int32, _P]),
     'emsa_se_scale_bwd_reduce_t': (c_int, [c_int32, _P, _P, _P, _P, c_int32, c_int64, c_int32, _P]),
+    'emsa_se_pair_mlp_fwd': (c_int, [_P] * 12 + [c_int32, c_int64, c_int32, c_int32, _P]),
+    # csrc/stem_stage.hip
+    'emsa_stem_stage_squeeze': (c_int, [_P] * 7 + [c_int32, c_int64, c_int32, _P]),
+    'emsa_stem_stage_fwd': (c_int, [_P] * 12 + [c_int32] * 4 + [_P]),
+    'emsa_stem_stage_bwd_splits': (c_int, [c_int32, c_int32]),
+    'emsa_stem_stage_bwd_reduce': (c_int, [_P] * 17 + [c_int32] * 4 + [_P]),
+    'emsa_stem_stage_bwd_finalize': (c_int, [_P] * 9 + [c_int32, c_int64, c_int32, _P]),
+    'emsa_stem_stage_bwd_apply': (c_int, [_P] * 26 + [c_int32] * 4 + [_P]),
     'emsa_cast_channels': (c_int, [c_int32, _P, c_int32, c_int32, _P, c_int32, c_int64, c_int32, _P]),
     'emsa_conv_stats_rows_t': (c_int, [c_int32, _GP]),
     'emsa_conv_igemm_t': (c_int, [c_int32, _GP, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, _P, c_int32,

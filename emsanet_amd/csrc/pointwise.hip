@@ -11,6 +11,7 @@
 
 #include <atomic>
 #include "common.h"
+#include "bn_math.h"
 
 namespace {
 
@@ -325,32 +326,6 @@ __global__ void bn_fold_kernel(const float* gamma, const float* beta, const floa
     shift[i] = beta[i] - rm[i] * sc;
     if (invstd) invstd[i] = is;
   }
-}
-
-// ---- the arithmetic of the BatchNorm passes, spelled out ----------------------------------------
-// One fma / mul / add per step, none left to the compiler's contraction heuristics: the general and
-// the fast form of a pass (below) must round alike, and what clang fuses depends on the code around
-// an expression (a product hoisted out of a loop is no longer fused into the sum behind it).
-__device__ __forceinline__ float bn_mul(float a, float b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
-__device__ __forceinline__ float bn_add(float a, float b) {
-#pragma clang fp contract(off)
-  return a + b;
-}
-// y = x * scale + shift
-__device__ __forceinline__ float bn_affine(float x, float sc, float sh) { return __builtin_fmaf(x, sc, sh); }
-// one term of sum g * xhat:  acc + (g * (x - mean)) * invstd
-__device__ __forceinline__ float bn_acc_xhat(float acc, float g, float x, float mu, float is) {
-  return __builtin_fmaf(bn_mul(g, bn_add(x, -mu)), is, acc);
-}
-// dx = gamma * invstd * (g - sum_g / N - xhat * sum_gxhat / N), gi = gamma * invstd (bn_mul)
-__device__ __forceinline__ float bn_dx_train(float g, float x, float mu, float is, float gi, float db,
-                                             float dg, float inv_count) {
-  const float xh = bn_mul(bn_add(x, -mu), is);
-  const float t = __builtin_fmaf(-db, inv_count, g);
-  return bn_mul(gi, __builtin_fmaf(-bn_mul(xh, dg), inv_count, t));
 }
 
 // ---- vector access per lane: 16 bytes = 4 fp32 or 8 16-bit channels ---------------------------
@@ -3319,6 +3294,22 @@ extern "C" int emsa_se_pair_fwd_t(int32_t dtype, const void* xa, const void* xb,
   EMSA_DISPATCH_DTYPE(dtype, T, return se_pair_fwd<T>((const T*)xa, (const T*)xb, ws, wts, gap, hid,
                                                       s, n, (long)hw, c, cr, (hipStream_t)stream));
   return EMSA_E_ARG;
+}
+// the second launch of emsa_se_pair_fwd_t alone: `ws` holds split sums somebody else produced in
+// channel_dot_kernel's layout and partition (stem_stage.hip sums the activation without storing it)
+extern "C" int emsa_se_pair_mlp_fwd(const float* ws, const float* w1a, const float* b1a,
+                                    const float* w2a, const float* b2a, const float* w1b,
+                                    const float* b1b, const float* w2b, const float* b2b,
+                                    float* gap, float* hid, float* s, int32_t n, int64_t hw,
+                                    int32_t c, int32_t cr, void* stream) {
+  if (!ws || !w1a || !b1a || !w2a || !b2a || !w1b || !b1b || !w2b || !b2b || !gap || !hid || !s)
+    return EMSA_E_ARG;
+  if (n < 1 || hw < 1 || c < 1 || cr < 1) return EMSA_E_SHAPE;
+  hipLaunchKernelGGL(se_mlp_pair_fwd_kernel, dim3(2 * n), dim3(256),
+                     (size_t)(c + cr) * sizeof(float), (hipStream_t)stream, ws,
+                     channel_splits((long)hw, n), 1.0f / (float)hw, w1a, b1a, w2a, b2a, w1b, b1b, w2b,
+                     b2b, gap, hid, s, n, c, cr);
+  return emsa_launch_status();
 }
 extern "C" int emsa_se_mlp_bwd(const float* gap, const float* w1, const float* w2,
                                const float* hid, const float* s, const float* ds, float* dgap,

@@ -1389,6 +1389,141 @@ def se_scale_bwd_apply(dout, s, dgap, extra=None):
     return dx
 
 
+# ---------------------------------------------------------------------------------------------
+# the half-resolution stage behind the two stem convolutions as four passes (csrc/stem_stage.hip)
+# ---------------------------------------------------------------------------------------------
+# BatchNorm + ReLU of both streams, the SE-add fusion and both max pools computed from the conv
+# outputs y_rgb / y_depth; the activations, their bit masks and the fused map are never stored.
+# EMSA_STEM_FUSE (read once): 0 / 1 forces it off / on; unset = the rule of nn.FusedEncoder (fp32
+# storage, training with batch statistics, two encoders with SE-add fusion, 64 channels, no skip
+# connection and no CutPlan cut at downsampling 2) for half-resolution maps of at least
+# EMSA_STEM_FUSE_MIN_MB (default 24 MiB, the floor of the bn1 fold): what the passes save is HBM
+# traffic, measured at 629 MB per map (profiles/stem_fuse_*); smaller maps keep the launches they had.
+# Forced on, the stage runs at every size.
+_STEM_FUSE_ENV = os.environ.get('EMSA_STEM_FUSE')
+_STEM_FUSE_MIN_BYTES = int(float(os.environ.get('EMSA_STEM_FUSE_MIN_MB', '24')) * (1 << 20))
+STEM_FUSE = None             # tests: True / False overrides the rule
+
+
+# forward passes that were asked to run the fused stage (switch forced on) in a configuration it
+# does not cover and ran today's kernels instead: 0 for the model bench.py trains
+STEM_FUSE_FALLBACKS = 0
+
+
+def _stem_fuse_fell_back():
+    global STEM_FUSE_FALLBACKS
+    STEM_FUSE_FALLBACKS += 1
+
+
+def stem_fuse_forced():
+    """True / False when the switch is forced, None when the rule decides"""
+    if STEM_FUSE is not None:
+        return bool(STEM_FUSE)
+    if _STEM_FUSE_ENV is not None:
+        return _STEM_FUSE_ENV != '0'
+    return None
+
+
+def stem_fuse_big_enough(x_nchw, c=64):
+    """the rule's size floor, from the network input: bytes of one fp32 map at half resolution"""
+    n, _, h, w = x_nchw.shape
+    return n * c * ((h + 1) // 2) * ((w + 1) // 2) * 4 >= _STEM_FUSE_MIN_BYTES
+
+
+def _stem_pair_check(y_rgb, y_depth):
+    n, c, h, w = y_rgb.shape
+    assert y_depth.shape == y_rgb.shape and y_rgb.dtype == y_depth.dtype == torch.float32
+    assert ld_of(y_rgb) == c and ld_of(y_depth) == c
+    return n, c, h, w
+
+
+def stem_stage_se(y_rgb, y_depth, aff_rgb, aff_depth, wa, wb):
+    """forward pass 1: squeeze of relu(y * scale + shift) of both streams + both excitation MLPs.
+    aff_* = (scale, shift), wa / wb as in se_pair_fwd -> (gap_a, gap_b, hid_a, hid_b, s_a, s_b),
+    bit-identical to se_pair_fwd on the materialised activations"""
+    n, c, h, w = _stem_pair_check(y_rgb, y_depth)
+    cr = wa[0].shape[0]
+    dev = y_rgb.device
+    L = _lib.lib()
+    gap, hid, s = _empty((2, n, c), dev), _empty((2, n, cr), dev), _empty((2, n, c), dev)
+    ws = _empty((2 * L.emsa_channel_ws_floats(n, h * w, c),), dev)
+    check(L.emsa_stem_stage_squeeze(_p(y_rgb), _p(y_depth), _p(aff_rgb[0]), _p(aff_rgb[1]),
+                                    _p(aff_depth[0]), _p(aff_depth[1]), _p(ws), n, h * w, c,
+                                    _stream()), 'emsa_stem_stage_squeeze')
+    check(L.emsa_se_pair_mlp_fwd(_p(ws), _p(wa[0]), _p(wa[1]), _p(wa[2]), _p(wa[3]), _p(wb[0]),
+                                 _p(wb[1]), _p(wb[2]), _p(wb[3]), _p(gap), _p(hid), _p(s), n, h * w,
+                                 c, cr, _stream()), 'emsa_se_pair_mlp_fwd')
+    return gap[0], gap[1], hid[0], hid[1], s[0], s[1]
+
+
+def stem_stage_fwd(y_rgb, y_depth, aff_rgb, aff_depth, s_rgb, s_depth):
+    """forward pass 2 -> P_f, idx_f, P_d, idx_d (the max pools of the fused map and of the depth
+    activation with their int8 argmax taps), bit-identical to se_scale_add + maxpool_fwd x2"""
+    n, c, h, w = _stem_pair_check(y_rgb, y_depth)
+    oh, ow = (h + 1) // 2, (w + 1) // 2
+    dev = y_rgb.device
+    pf, pd = act_empty(n, c, oh, ow, dev), act_empty(n, c, oh, ow, dev)
+    idx = _empty((2, n, oh, ow, c), dev, torch.int8)
+    check(_lib.lib().emsa_stem_stage_fwd(_p(y_rgb), _p(y_depth), _p(aff_rgb[0]), _p(aff_rgb[1]),
+                                         _p(aff_depth[0]), _p(aff_depth[1]), _p(s_rgb), _p(s_depth),
+                                         _p(pf), _p(idx[0]), _p(pd), _p(idx[1]), n, h, w, c,
+                                         _stream()), 'emsa_stem_stage_fwd')
+    return pf, idx[0], pd, idx[1]
+
+
+def stem_stage_bwd_reduce(gf, idx_f, gd, idx_d, y_rgb, y_depth, aff_rgb, aff_depth, st_rgb, st_depth):
+    """backward pass 1.  gf / gd = gradients of P_f / P_d, st_* = (mean, invstd) -> per-image sums
+    (fp64 [n][12][c], for stem_stage_bwd_finalize), ds_rgb, ds_depth ([n][c], for se_mlp_bwd)"""
+    n, c, h, w = _stem_pair_check(y_rgb, y_depth)
+    assert gf.dtype == gd.dtype == torch.float32 and ld_of(gf) == c and ld_of(gd) == c
+    assert tuple(gf.shape) == tuple(gd.shape) == (n, c, (h + 1) // 2, (w + 1) // 2)
+    dev = y_rgb.device
+    L = _lib.lib()
+    splits = L.emsa_stem_stage_bwd_splits(h, w)
+    ws = _empty((n, splits, 12, c), dev)
+    sums = _empty((n, 12, c), dev, torch.float64)
+    ds = _empty((2, n, c), dev)
+    check(L.emsa_stem_stage_bwd_reduce(_p(gf), _p(idx_f), _p(gd), _p(idx_d), _p(y_rgb), _p(y_depth),
+                                       _p(aff_rgb[0]), _p(aff_rgb[1]), _p(aff_depth[0]),
+                                       _p(aff_depth[1]), _p(st_rgb[0]), _p(st_rgb[1]),
+                                       _p(st_depth[0]), _p(st_depth[1]), _p(ws), _p(sums), _p(ds), n,
+                                       h, w, c, _stream()), 'emsa_stem_stage_bwd_reduce')
+    return sums, ds[0], ds[1]
+
+
+def stem_stage_bwd_finalize(sums, hw, s_rgb, s_depth, dgap_rgb, dgap_depth, out_rgb=None,
+                            out_depth=None):
+    """dgamma / dbeta of both BatchNorms -> (dg_rgb, db_rgb, dg_depth, db_depth); out_* = (dg, db)
+    destinations (the parameters' flat gradient-bucket views) or None"""
+    n, c = s_rgb.shape
+    res = []
+    for out in (out_rgb, out_depth):
+        if out is None or out[0] is None or out[1] is None:
+            buf = _empty((2, c), s_rgb.device)
+            out = (buf[0], buf[1])
+        res += [out[0], out[1]]
+    check(_lib.lib().emsa_stem_stage_bwd_finalize(_p(sums), _p(s_rgb), _p(s_depth), _p(dgap_rgb),
+                                                  _p(dgap_depth), _p(res[0]), _p(res[1]), _p(res[2]),
+                                                  _p(res[3]), n, hw, c, _stream()),
+          'emsa_stem_stage_bwd_finalize')
+    return tuple(res)
+
+
+def stem_stage_bwd_apply(gf, idx_f, gd, idx_d, y_rgb, y_depth, aff_rgb, aff_depth, st_rgb, st_depth,
+                         gamma_rgb, gamma_depth, s_rgb, s_depth, dgap_rgb, dgap_depth, dgb):
+    """backward pass 2 -> dy_rgb, dy_depth; dgb = the result of stem_stage_bwd_finalize"""
+    n, c, h, w = _stem_pair_check(y_rgb, y_depth)
+    dev = y_rgb.device
+    dy_rgb, dy_depth = act_empty(n, c, h, w, dev), act_empty(n, c, h, w, dev)
+    check(_lib.lib().emsa_stem_stage_bwd_apply(
+        _p(gf), _p(idx_f), _p(gd), _p(idx_d), _p(y_rgb), _p(y_depth), _p(aff_rgb[0]), _p(aff_rgb[1]),
+        _p(aff_depth[0]), _p(aff_depth[1]), _p(st_rgb[0]), _p(st_rgb[1]), _p(st_depth[0]),
+        _p(st_depth[1]), _p(gamma_rgb), _p(gamma_depth), _p(s_rgb), _p(s_depth), _p(dgap_rgb),
+        _p(dgap_depth), _p(dgb[0]), _p(dgb[1]), _p(dgb[2]), _p(dgb[3]), _p(dy_rgb), _p(dy_depth), n,
+        h, w, c, _stream()), 'emsa_stem_stage_bwd_apply')
+    return dy_rgb, dy_depth
+
+
 def _two(name, feat, out_f32, *args):
     """kernels at the model boundary: features in the dtype of `feat`, output-side tensors fp32
     when `out_f32` (always the case for an fp32 engine)"""

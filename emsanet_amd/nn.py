@@ -216,15 +216,21 @@ class ResNetNBt1D(nn.Module):
         # the fp32 network input is converted when the stem packs it
         self.compute_dtype = torch.float32
 
-    def forward_stage(self, i, x):
+    def forward_stage(self, i, x, pooled=False):
+        """pooled: stage 0 was ops.StemStageFunction, which hands on the max-pooled map"""
         if i == 0:
             if _fast_eval(self):
                 return ops.stem_eval(x, self._stem, self.compute_dtype)
             return ops.StemFunction.apply(x, self._stem, self.conv1.weight, self.bn1.weight,
                                           self.bn1.bias, self.conv1.bias, self.compute_dtype)
-        if i == 1:
+        if i == 1 and not pooled:
             x = ops.MaxPoolFunction.apply(x)
         return getattr(self, f'layer{i}')(x)
+
+    def stem_conv(self, x):
+        """the convolution of stage 0 alone -> (y, BatchNorm statistics rows), for the fused stage"""
+        return ops.StemConvFunction.apply(x, self._stem, self.conv1.weight, self.conv1.bias,
+                                          self.compute_dtype)
 
 
 class SqueezeAndExcitation(nn.Module):
@@ -357,6 +363,7 @@ class FusedEncoder(nn.Module):
     def forward(self, inputs, plan=None):
         """plan: a CutPlan (segmented backward); skips / outputs are then returned as
         (tensor, producing stage) pairs for the caller to cut at the decoder boundary"""
+        fused0 = self._stem_stage_fused(plan, inputs.get('rgb'))
         if self.backbone_rgbd is not None:
             return self._forward_single('rgbd', self.backbone_rgbd, inputs['rgbd'], plan)
         rgb, depth = inputs.get('rgb'), inputs.get('depth')
@@ -374,6 +381,9 @@ class FusedEncoder(nn.Module):
             register_stream(cur)
             register_stream(side)
         for i, ds in enumerate(bb.stage_downsamplings):
+            if i == 0 and fused0:
+                rgb, depth = self._forward_stem_stage(rgb, depth, dual and (cur, side))
+                continue
             if dual:
                 # the two encoders' stages are independent until the fusion: the depth stage runs
                 # on a second stream (autograd replays its backward there too), so the small
@@ -382,16 +392,16 @@ class FusedEncoder(nn.Module):
                 # (host order rgb, then depth -- as without the second stream: tests replay the
                 #  recorded ReLU decisions in call order)
                 side.wait_stream(cur)
-                rgb = self.backbone_rgb.forward_stage(i, rgb)
+                rgb = self.backbone_rgb.forward_stage(i, rgb, pooled=fused0)
                 with torch.cuda.stream(side):
-                    depth = self.backbone_depth.forward_stage(i, depth)
+                    depth = self.backbone_depth.forward_stage(i, depth, pooled=fused0)
                 cur.wait_stream(side)
                 depth.record_stream(cur)
             else:
                 if rgb is not None:
-                    rgb = self.backbone_rgb.forward_stage(i, rgb)
+                    rgb = self.backbone_rgb.forward_stage(i, rgb, pooled=fused0)
                 if depth is not None:
-                    depth = self.backbone_depth.forward_stage(i, depth)
+                    depth = self.backbone_depth.forward_stage(i, depth, pooled=fused0)
             if self.two:
                 rgb, depth = self.fusion_modules[i](rgb, depth)
             if ds in self.skip_downsamplings:
@@ -408,6 +418,50 @@ class FusedEncoder(nn.Module):
         outs = {k: (v if plan is None else (v, last))
                 for k, v in (('rgb', rgb), ('depth', depth)) if v is not None}
         return outs, skips
+
+    def _stem_stage_fused(self, plan, x=None):
+        """stage 0 as ops.StemStageFunction (csrc/stem_stage.hip)?  The rule is the set of
+        configurations those kernels cover, at map sizes from Fn.stem_fuse_big_enough on;
+        Fn.STEM_FUSE / EMSA_STEM_FUSE force it off, or on at every size -- and a configuration the
+        kernels do not cover then still runs today's kernels and is counted in
+        Fn.STEM_FUSE_FALLBACKS."""
+        forced = Fn.stem_fuse_forced()
+        if forced is False:
+            return False
+        r, d = self.backbone_rgb, self.backbone_depth
+        ok = self.two and all(
+            bb.training and bb._stem.brt.batch_stats() and bb.compute_dtype == torch.float32 and
+            bb.conv1.out_channels == 64 for bb in (r, d)) and \
+            2 not in self.skip_downsamplings and (plan is None or 0 not in plan.stages)
+        if forced and not ok:
+            Fn._stem_fuse_fell_back()
+        return bool(ok and (forced or (x is not None and Fn.stem_fuse_big_enough(x))))
+
+    def _forward_stem_stage(self, rgb, depth, streams):
+        """stage 0 with the fused half-resolution stage: the two stem convolutions on their two
+        streams, then BatchNorm + ReLU, SE-add fusion and both max pools as one Function on the
+        calling stream -> the inputs of layer1"""
+        r, d = self.backbone_rgb, self.backbone_depth
+        if streams:
+            cur, side = streams
+            side.wait_stream(cur)
+            y_rgb, st_rgb = r.stem_conv(rgb)
+            with torch.cuda.stream(side):
+                y_depth, st_depth = d.stem_conv(depth)
+            cur.wait_stream(side)
+            y_depth.record_stream(cur)
+            st_depth.record_stream(cur)
+        else:
+            (y_rgb, st_rgb), (y_depth, st_depth) = r.stem_conv(rgb), d.stem_conv(depth)
+        f = self.fusion_modules[0]
+        pf, pd = ops.StemStageFunction.apply(
+            y_rgb, st_rgb, y_depth, st_depth, r._stem, d._stem, r.bn1.weight, r.bn1.bias,
+            d.bn1.weight, d.bn1.bias, *ops._se_params(f.se_rgb), *ops._se_params(f.se_depth))
+        if streams:
+            # (allocated on the calling stream, read by the depth encoder's layer1 and its weight
+            #  gradients on the second one: the caching allocator must not recycle it early)
+            pd.record_stream(side)
+        return pf, pd
 
     def _twin_eval_ok(self, plan, x=None):
         if not (self.two and plan is None and _fast_eval(self) and twin_launches(x)):

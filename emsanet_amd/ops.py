@@ -1369,6 +1369,110 @@ def stem_eval(x_nchw, rt, dtype=torch.float32):
 
 
 # ---------------------------------------------------------------------------------------------
+# the stage behind the two stems as four passes (csrc/stem_stage.hip; dispatch: nn.FusedEncoder)
+# ---------------------------------------------------------------------------------------------
+class StemConvFunction(Function):
+    """the convolution half of StemFunction: y and its BatchNorm statistics rows forward, the weight
+    gradient from dy backward.  One per stream, so the two stem convolutions and their weight
+    gradients stay on their two HIP streams; everything between y and layer1 is StemStageFunction."""
+
+    @staticmethod
+    def forward(ctx, x_nchw, rt, weight, bias=None, dtype=torch.float32):
+        n, c, h, w = x_nchw.shape
+        xp = Fn.stem_pack_input(x_nchw.detach().float(), dtype)
+        b = bias.detach() if bias is not None else None      # [U] Spec.STEM_BIAS
+        y, stats = Fn.stem_fwd(xp, rt.packed(dtype), rt.spec, n, h, w, want_stats=True, bias=b)
+        ctx.rt, ctx.hw, ctx.xp, ctx.has_bias = rt, (n, h, w), xp, bias is not None
+        ctx.mark_non_differentiable(stats)
+        ctx.set_materialize_grads(False)      # (no zeros tensor for the statistics rows)
+        return y, stats
+
+    @staticmethod
+    @once_differentiable
+    @_traced
+    def backward(ctx, dy, _dstats):
+        rt, xp = ctx.rt, ctx.xp
+        ctx.xp = None
+        n, h, w = ctx.hw
+        dy = Fn.as_act(dy, dense=True)
+        _trace_grad(rt.conv, dy)
+        res = Fn.stem_wgrad(xp, dy, rt.spec, n, h, w, rt.conv.weight,
+                            out=grad_target(rt.conv.weight), want_bias=ctx.has_bias)
+        dw, dbias = res if ctx.has_bias else (res, None)
+        return None, None, dw, dbias, None
+
+
+class StemStageFunction(Function):
+    """(y_rgb, y_depth) -> (maxpool(a_rgb * SE_rgb + a_depth * SE_depth), maxpool(a_depth)) with
+    a = relu(BatchNorm(y)), batch statistics: what StemFunction's BatchNorm half, SEAddFunction and
+    two MaxPoolFunctions compute, in two passes over y forward and two backward.  Saved for the
+    backward pass: y_rgb, y_depth, the two argmax maps and per-channel / per-image vectors."""
+
+    @staticmethod
+    def forward(ctx, y_rgb, stats_rgb, y_depth, stats_depth, rt_rgb, rt_depth, gamma_r, beta_r,
+                gamma_d, beta_d, w1r, b1r, w2r, b2r, w1d, b1d, w2d, b2d):
+        y_rgb, y_depth = Fn.as_act(y_rgb, dense=True), Fn.as_act(y_depth, dense=True)
+        n, c, h, w = y_rgb.shape
+        aff, st = [], []
+        for rt, stats in ((rt_rgb, stats_rgb), (rt_depth, stats_depth)):
+            scale, shift, mean, invstd = rt.brt.forward_stats(stats, n * h * w)
+            aff.append((scale, shift))
+            st.append((mean, invstd))
+        if MASK_TRACE is not None:            # (tests: the activations exist for the trace only)
+            for y, (scale, shift) in zip((y_rgb, y_depth), aff):
+                _trace_mask('stem', Fn.bn_act(y, scale, shift, None, None, ACT_RELU))
+        flat = lambda t: t.detach().reshape(t.shape[0], -1)   # noqa: E731
+        gr, gd, hr, hd, sr, sd = Fn.stem_stage_se(
+            y_rgb, y_depth, aff[0], aff[1], (flat(w1r), b1r.detach(), flat(w2r), b2r.detach()),
+            (flat(w1d), b1d.detach(), flat(w2d), b2d.detach()))
+        _trace_mask('se.rgb', hr)
+        _trace_mask('se.depth', hd)
+        pf, idx_f, pd, idx_d = Fn.stem_stage_fwd(y_rgb, y_depth, aff[0], aff[1], sr, sd)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(y_rgb, y_depth)
+        ctx.rts = (rt_rgb, rt_depth)
+        ctx.saved = (idx_f, idx_d, aff, st, (gr, hr, sr, flat(w1r), flat(w2r)),
+                     (gd, hd, sd, flat(w1d), flat(w2d)))
+        ctx.shapes = (w1r.shape, w2r.shape)
+        return pf, pd
+
+    @staticmethod
+    @once_differentiable
+    @_traced
+    def backward(ctx, g_f, g_d):
+        y_rgb, y_depth = ctx.saved_tensors
+        idx_f, idx_d, aff, st, se_r, se_d = ctx.saved
+        ctx.saved = None
+        rt_rgb, rt_depth = ctx.rts
+        n, c, h, w = y_rgb.shape
+        pooled = (n, (h + 1) // 2, (w + 1) // 2, c)
+
+        def grad(g):                     # (an unused output arrives as None)
+            if g is None:
+                return torch.zeros(pooled, device=y_rgb.device).permute(0, 3, 1, 2)
+            g = Fn.as_act(g, dense=True)
+            return g if g.dtype == torch.float32 else Fn.cast(g, torch.float32)
+        g_f, g_d = grad(g_f), grad(g_d)
+        sums, ds_r, ds_d = Fn.stem_stage_bwd_reduce(g_f, idx_f, g_d, idx_d, y_rgb, y_depth, aff[0],
+                                                    aff[1], st[0], st[1])
+        s1, s2 = ctx.shapes
+        se_grads, dgaps = [], []
+        for (gap, hid, s, w1, w2), ds in ((se_r, ds_r), (se_d, ds_d)):
+            dgap, dw1, db1, dw2, db2 = Fn.se_mlp_bwd(gap, w1, w2, hid, s, ds)
+            dgaps.append(dgap)
+            se_grads += [dw1.reshape(s1), db1, dw2.reshape(s2), db2]
+        tr, td = _bn_targets(rt_rgb.brt), _bn_targets(rt_depth.brt)
+        dgb = Fn.stem_stage_bwd_finalize(
+            sums, h * w, se_r[2], se_d[2], dgaps[0], dgaps[1],
+            (tr.get('dg_out'), tr.get('db_out')), (td.get('dg_out'), td.get('db_out')))
+        dy_rgb, dy_depth = Fn.stem_stage_bwd_apply(
+            g_f, idx_f, g_d, idx_d, y_rgb, y_depth, aff[0], aff[1], st[0], st[1],
+            rt_rgb.brt.bn.weight.detach(), rt_depth.brt.bn.weight.detach(), se_r[2], se_d[2],
+            dgaps[0], dgaps[1], dgb)
+        return (dy_rgb, None, dy_depth, None, None, None, dgb[0], dgb[1], dgb[2], dgb[3], *se_grads)
+
+
+# ---------------------------------------------------------------------------------------------
 # max pool
 # ---------------------------------------------------------------------------------------------
 class MaxPoolFunction(Function):

@@ -1134,6 +1134,63 @@ int emsa_se_pair_fwd_t(int32_t dtype, const void* xa, const void* xb, float* ws,
                        void* stream);
 int emsa_channel_mean_t(int32_t dtype, const void* x, float* gap, float* ws, int32_t n, int64_t
     hw, int32_t c, void* stream);
+/* the second launch of emsa_se_pair_fwd_t alone: ws = [2][n][splits][c] split sums in the layout and
+ * partition of emsa_channel_ws_floats(n, hw, c), produced by emsa_stem_stage_squeeze */
+int emsa_se_pair_mlp_fwd(const float* ws, const float* w1a, const float* b1a, const float* w2a,
+                         const float* b2a, const float* w1b, const float* b1b, const float* w2b,
+                         const float* b2b, float* gap, float* hid, float* s, int32_t n, int64_t hw,
+                         int32_t c, int32_t cr, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The half-resolution stage behind the two stem convolutions (csrc/stem_stage.hip): BatchNorm +
+ * ReLU of both streams, the SE-add fusion and both 3x3/2 max pools in two passes over the conv
+ * outputs y_rgb / y_depth forward and two backward; the activations, their masks and the fused map
+ * are never stored.  fp32, c = 64, batch statistics only: anything else is EMSA_E_SHAPE before any
+ * launch.  Per-channel vectors are [c], s / dgap / gap [n][c]; h, w = size of y.
+ *   squeeze: ws (2 * emsa_channel_ws_floats floats) := split sums of relu(y * scale + shift), for
+ *            emsa_se_pair_mlp_fwd; bit-equal to emsa_se_pair_fwd_t on the stored activations
+ *   fwd:     pf = maxpool(a_rgb s_rgb + a_depth s_depth), pd = maxpool(a_depth), int8 argmax taps;
+ *            bit-equal to emsa_se_scale_add_fwd + emsa_maxpool3x3s2_fwd x2
+ *   bwd_reduce: gf / gd = gradients of pf / pd.  ws: n * emsa_stem_stage_bwd_splits(h, w) * 12 * c
+ *            floats, sums: n * 12 * c doubles, ds: [2][n][c] (sum dout a per stream, for
+ *            emsa_se_mlp_bwd)
+ *   bwd_finalize: dgamma / dbeta of both BatchNorms from `sums`, s and the SE dgap
+ *   bwd_apply: dy_rgb, dy_depth (the gradients the stem weight gradients read)
+ * ------------------------------------------------------------------------------------------ */
+int emsa_stem_stage_squeeze(const float* y_rgb, const float* y_depth, const float* scale_rgb,
+                            const float* shift_rgb, const float* scale_depth,
+                            const float* shift_depth, float* ws, int32_t n, int64_t hw, int32_t c,
+                            void* stream);
+int emsa_stem_stage_fwd(const float* y_rgb, const float* y_depth, const float* scale_rgb,
+                        const float* shift_rgb, const float* scale_depth, const float* shift_depth,
+                        const float* s_rgb, const float* s_depth, float* pf, int8_t* idx_f,
+                        float* pd, int8_t* idx_d, int32_t n, int32_t h, int32_t w, int32_t c,
+                        void* stream);
+int emsa_stem_stage_bwd_splits(int32_t h, int32_t w);
+int emsa_stem_stage_bwd_reduce(const float* gf, const int8_t* idx_f, const float* gd,
+                               const int8_t* idx_d, const float* y_rgb, const float* y_depth,
+                               const float* scale_rgb, const float* shift_rgb,
+                               const float* scale_depth, const float* shift_depth,
+                               const float* mean_rgb, const float* invstd_rgb,
+                               const float* mean_depth, const float* invstd_depth, float* ws,
+                               double* sums, float* ds, int32_t n, int32_t h, int32_t w, int32_t c,
+                               void* stream);
+int emsa_stem_stage_bwd_finalize(const double* sums, const float* s_rgb, const float* s_depth,
+                                 const float* dgap_rgb, const float* dgap_depth, float* dgamma_rgb,
+                                 float* dbeta_rgb, float* dgamma_depth, float* dbeta_depth,
+                                 int32_t n, int64_t hw, int32_t c, void* stream);
+int emsa_stem_stage_bwd_apply(const float* gf, const int8_t* idx_f, const float* gd,
+                              const int8_t* idx_d, const float* y_rgb, const float* y_depth,
+                              const float* scale_rgb, const float* shift_rgb,
+                              const float* scale_depth, const float* shift_depth,
+                              const float* mean_rgb, const float* invstd_rgb,
+                              const float* mean_depth, const float* invstd_depth,
+                              const float* gamma_rgb, const float* gamma_depth, const float* s_rgb,
+                              const float* s_depth, const float* dgap_rgb, const float* dgap_depth,
+                              const float* dgamma_rgb, const float* dbeta_rgb,
+                              const float* dgamma_depth, const float* dbeta_depth, float* dy_rgb,
+                              float* dy_depth, int32_t n, int32_t h, int32_t w, int32_t c,
+                              void* stream);
 int emsa_se_scale_bwd_reduce_t(int32_t dtype, const void* dout, const void* x, float* ds, float*
     ws, int32_t n, int64_t hw, int32_t c, void* stream);
 int emsa_cast_channels(int32_t src_dtype, const void* x, int32_t ld_x, int32_t dst_dtype, void*
