@@ -34,6 +34,13 @@ def _empty(shape, device, dtype=torch.float32):
     return t
 
 
+def _zeros(shape, device, dtype=torch.float32):
+    """zero-initialised twin of `_empty` (accumulators of atomics, operands whose padding must read as
+    zero): the same single allocation point, so that the tests' guarded allocator sees these buffers
+    too.  Never poisoned: the zeros are the contract."""
+    return torch.zeros(shape, device=device, dtype=dtype)
+
+
 # storage types of the activation tensors (EMSA_DT_* of include/emsanet_hip.h): fp32 is the
 # reference's arithmetic (BASELINE configs[1]), bf16 the mixed-precision training path (configs[2]),
 # bf16 / fp16 the 16-bit inference path (configs[4])
@@ -64,7 +71,7 @@ def act_empty(n, c, h, w, device, ld=None, dtype=torch.float32):
 
 
 def act_zeros(n, c, h, w, device, dtype=torch.float32):
-    return torch.zeros((n, h, w, c), device=device, dtype=dtype).permute(0, 3, 1, 2)
+    return _zeros((n, h, w, c), device, dtype).permute(0, 3, 1, 2)
 
 
 def ld_of(t):
@@ -197,7 +204,7 @@ def pack_weight_t(w, dtype, fwd=True, dgrad=False, cout_total=None, cout_off=0, 
     cin_total = cin_total or cin
     n = kh * kw * cout_total * cin_total
     padded = cout_total != cout or cin_total != cin
-    mk = (lambda: torch.zeros(n, device=w.device, dtype=dtype)) if padded \
+    mk = (lambda: _zeros((n,), w.device, dtype)) if padded \
         else (lambda: _empty((n,), w.device, dtype))
     if fwd and out_fwd is None:
         out_fwd = mk()
@@ -290,7 +297,7 @@ def pack_weight(w, mode, cout_total=None, cout_off=0, cin_total=None, cin_off=0,
     cin_total = cin_total or cin
     if out is None:
         if cout_total != cout or cin_total != cin:
-            out = torch.zeros(kh * kw * cout_total * cin_total, device=w.device, dtype=torch.float32)
+            out = _zeros((kh * kw * cout_total * cin_total,), w.device)
         else:
             out = _empty(kh * kw * cout_total * cin_total, w.device)
     fn = _lib.lib().emsa_pack_weight_fwd if mode == 'fwd' else _lib.lib().emsa_pack_weight_dgrad
@@ -399,7 +406,7 @@ def _wino2d_buf(n_ch, k_ch, dev):
     # the padding of a k_ch that is no multiple of 8 is never read by the kernel; zero, so that
     # two packs of the same weights compare equal
     n = wino2d_numel(n_ch, k_ch)
-    return _empty((n,), dev) if k_ch % 8 == 0 else torch.zeros(n, device=dev, dtype=torch.float32)
+    return _empty((n,), dev) if k_ch % 8 == 0 else _zeros((n,), dev)
 
 
 def pack_wino2d(w, fwd=True, dgrad=False):
@@ -496,8 +503,8 @@ def conv_fwd(x, wp, spec, bias=None, want_stats=False, scale=None, shift=None, r
                              "BatchNorm (no output affine / residual)")
     if wino_u is not None:
         if want_relu_bits and act == ACT_RELU:
-            bits = torch.empty(L.emsa_conv_relu_bits_words(n * oh * ow, spec.cout),
-                               device=x.device, dtype=torch.int64)
+            bits = _empty((L.emsa_conv_relu_bits_words(n * oh * ow, spec.cout),), x.device,
+                          torch.int64)
         if in_affine is not None:
             check(L.emsa_conv1d_wino_inbn(g, _p(x), _p(wino_u), _p(out), _p(bias), _p(stats),
                                           _p(in_affine[0]), _p(in_affine[1]), act, _p(bits),
@@ -994,7 +1001,7 @@ def conv_wgrad(x, dy, spec, want_bias, like=None, two_pass=None, dw_out=None, db
             dw = buf[:nw]
             db = buf[nw:] if want_bias else None
     else:
-        buf = torch.zeros(nw + nb, device=x.device, dtype=torch.float32)
+        buf = _zeros((nw + nb,), x.device)
         ws = None
         dw = buf[:nw]
         db = buf[nw:] if want_bias else None
@@ -1156,6 +1163,8 @@ def stem_fwd(xp, wpk, spec, n, h, w, want_stats=True, bias=None):
     stats = None
     if want_stats:
         rows = call_t('emsa_conv_stats_rows', code, g)
+        if rows <= 0:
+            check(rows or -1, 'emsa_conv_stats_rows(stem)')
         stats = _empty((3, rows, spec.cout), xp.device)
     prof_flops(2.0 * n * oh * ow * spec.cout * 49 * spec.cin)
     check(call_t('emsa_conv_igemm', code, g, _p(xp), _p(wpk), _p(out), _p(bias), _p(stats), None,
@@ -1178,7 +1187,7 @@ def stem_wgrad(xp, dy, spec, n, h, w, like, out=None, want_bias=False):
     """-> dw (OIHW), or (dw, dbias) with want_bias"""
     g = spec.geom(n, h, w, ld_of(dy))
     nw = spec.taps * spec.cout * 32
-    buf = torch.zeros(nw + (spec.cout if want_bias else 0), device=dy.device, dtype=torch.float32)
+    buf = _zeros((nw + (spec.cout if want_bias else 0),), dy.device)
     dwp = buf[:nw]
     db = buf[nw:] if want_bias else None
     oh, ow = spec.out_hw(h, w)
@@ -1227,8 +1236,7 @@ def bn_act(x, scale, shift, drop=None, residual=None, act=ACT_NONE, want_mask=Fa
     L = _lib.lib()
     bits = None
     if want_mask and act == ACT_RELU:
-        bits = torch.empty(L.emsa_relu_mask_words(n * c * h * w), device=x.device,
-                           dtype=torch.int64)
+        bits = _empty((L.emsa_relu_mask_words(n * c * h * w),), x.device, torch.int64)
     check(call_t('emsa_bn_act_fwd', dt(x), _p(x), _p(y), _p(scale), _p(shift), _p(drop),
                  _p(residual), n, h * w, c, act, _p(bits), _stream()), 'emsa_bn_act_fwd')
     return (y, bits) if want_mask else y
@@ -1576,7 +1584,7 @@ def up2x_dw_bwd(dy, x, wdw, need_dx=True):
     if not out_f32 and dy.dtype != x.dtype:
         raise _lib.EmsaError(f"up-sampling gradient {dy.dtype} for {x.dtype} features")
     dx = act_empty(n, c, h, w, x.device, dtype=x.dtype) if need_dx else None
-    dwb = torch.zeros(c * 10, device=x.device, dtype=torch.float32)
+    dwb = _zeros((c * 10,), x.device)
     dw, db = dwb[:c * 9], dwb[c * 9:]
     if UP2X_FUSED_BWD and _lib.lib().emsa_up2x_dw3x3_bwd_supported(c, x.element_size()):
         # one LDS-tiled pass over dy for dx, dw and db

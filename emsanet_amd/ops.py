@@ -345,8 +345,8 @@ class PackPlan:
                        Fn.wino2d_numel(rt.spec.cin, rt.spec.cout)) for rt in w2_rts]
         w2sizes = [nel * 4 * (2 if rt.conv.weight.requires_grad else 1)
                    for rt, nel in zip(w2_rts, w2numel)]
-        arena = torch.empty(sum(a + b for _, a, b in sizes) + sum(fsizes) + sum(w2sizes), device=dev,
-                            dtype=torch.uint8)
+        arena = Fn._empty((sum(a + b for _, a, b in sizes) + sum(fsizes) + sum(w2sizes),), dev,
+                          torch.uint8)
         views, off, blk = [], 0, 0
         for j, (rt, (per, a, b)) in enumerate(zip(self.rts, sizes)):
             w = rt.conv.weight
@@ -407,9 +407,9 @@ class PackPlan:
             wino = m.wino and not half
             numel = taps * sp.cout * sp.cin
             per = numel * 4 // 3 if wino else numel
-            d0 = torch.zeros(per, device=dev, dtype=dtype)          # forward operand / Winograd U
-            d1 = torch.zeros(per, device=dev, dtype=dtype)          # data-gradient operand / U
-            bias = torch.zeros(sp.cout, device=dev, dtype=torch.float32) if m.has_bias else None
+            d0 = Fn._zeros((per,), dev, dtype)          # forward operand / Winograd U
+            d1 = Fn._zeros((per,), dev, dtype)          # data-gradient operand / U
+            bias = Fn._zeros((sp.cout,), dev) if m.has_bias else None
             kind = Fn.DT[dtype] + 1 if half else (1 if wino else 0)
             for q, co, ci in m.placements:
                 w4 = m._w4(q)
@@ -425,8 +425,8 @@ class PackPlan:
                     j += 1
             d2 = d3 = None
             if wino and m.wino2d:
-                d2 = torch.zeros(Fn.wino2d_numel(sp.cout, sp.cin), device=dev, dtype=dtype)   # U2 forward
-                d3 = torch.zeros(Fn.wino2d_numel(sp.cin, sp.cout), device=dev, dtype=dtype)   # data gradient
+                d2 = Fn._zeros((Fn.wino2d_numel(sp.cout, sp.cin),), dev, dtype)   # U2 forward
+                d3 = Fn._zeros((Fn.wino2d_numel(sp.cin, sp.cout),), dev, dtype)   # data gradient
                 for q, co, ci in m.placements:
                     w4 = m._w4(q)
                     cout, cin, kh, kw = w4.shape
@@ -1149,8 +1149,7 @@ class MultiConvRT:
 
     def _packed_fwd(self):
         s = self.spec
-        wp = torch.zeros(s.kh * s.kw * s.cout * s.cin, device=self.placements[0][0].weight.device,
-                         dtype=torch.float32)
+        wp = Fn._zeros((s.kh * s.kw * s.cout * s.cin,), self.placements[0][0].weight.device)
         for m, co, ci in self.placements:
             Fn.pack_weight(self._w4(m).detach(), 'fwd', s.cout, co, s.cin, ci, out=wp)
         return wp
@@ -1174,8 +1173,7 @@ class MultiConvRT:
         key = self._key_now()
         if key != self._key:
             s = self.spec
-            wp = torch.zeros(s.kh * s.kw * s.cout * s.cin, device=self.placements[0][0].weight.device,
-                             dtype=torch.float32)
+            wp = Fn._zeros((s.kh * s.kw * s.cout * s.cin,), self.placements[0][0].weight.device)
             for m, co, ci in self.placements:
                 Fn.pack_weight(self._w4(m).detach(), 'fwd', s.cout, co, s.cin, ci, out=wp)
             bias = self._bias_vec(wp.device) if self.has_bias else None
@@ -1191,7 +1189,7 @@ class MultiConvRT:
         if ent is None or ent[0] != key:
             s = self.spec
             dev = self.placements[0][0].weight.device
-            wp = torch.zeros(s.kh * s.kw * s.cout * s.cin, device=dev, dtype=dtype)
+            wp = Fn._zeros((s.kh * s.kw * s.cout * s.cin,), dev, dtype)
             for m, co, ci in self.placements:
                 Fn.pack_weight_t(self._w4(m).detach(), dtype, True, False, s.cout, co, s.cin, ci,
                                  out_fwd=wp)
@@ -1241,8 +1239,7 @@ class MultiConvRT:
 
     def packed_dgrad(self, dtype=torch.float32):
         s = self.spec
-        wp = torch.zeros(s.kh * s.kw * s.cout * s.cin, device=self.placements[0][0].weight.device,
-                         dtype=dtype)
+        wp = Fn._zeros((s.kh * s.kw * s.cout * s.cin,), self.placements[0][0].weight.device, dtype)
         for m, co, ci in self.placements:
             if dtype == torch.float32:
                 Fn.pack_weight(self._w4(m).detach(), 'dgrad', s.cout, co, s.cin, ci, out=wp)

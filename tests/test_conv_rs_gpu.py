@@ -10,6 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from guard import guard_allocations  # noqa: F401  (autouse: poisoned, guard-banded allocations)
 from util import DEV, close, rnd, to_act
 
 pytestmark = pytest.mark.gpu

@@ -12,6 +12,7 @@ time.  Tolerances are those of tests/test_loss.py: loss 1e-5 relative, gradient 
 import pytest
 import torch
 
+from guard import guard_allocations  # noqa: F401  (autouse: poisoned, guard-banded allocations)
 from util import DEV, to_act
 
 pytestmark = pytest.mark.gpu

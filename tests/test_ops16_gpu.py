@@ -12,6 +12,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from guard import guard_allocations  # noqa: F401  (autouse: poisoned, guard-banded allocations)
 from util import DEV, close, rnd
 
 pytestmark = pytest.mark.gpu
@@ -529,7 +530,7 @@ def test_bn_fast_kernels_are_bit_identical_to_the_general_ones(tmp_path):
     outs = {}
     for flag in ('1', '0'):
         path = str(tmp_path / f'bn_{flag}.pt')
-        env = dict(os.environ, EMSA_BN_FAST=flag)
+        env = dict(os.environ, EMSA_BN_FAST=flag, EMSA_POISON='1')
         r = subprocess.run([sys.executable, '-c', _BN_FAST_CODE, path], cwd=root, env=env,
                            capture_output=True, text=True, timeout=600)
         assert 'BN_DUMP_OK' in r.stdout, r.stderr[-3000:]
@@ -593,7 +594,7 @@ def test_index_width_variants_are_bit_identical(tmp_path):
     for flag in ('1', '0'):
         path = str(tmp_path / f'idx_{flag}.pt')
         r = subprocess.run([sys.executable, '-c', _IDX_CODE, path], cwd=root,
-                           env=dict(os.environ, EMSA_IDX32=flag), capture_output=True, text=True,
+                           env=dict(os.environ, EMSA_IDX32=flag, EMSA_POISON='1'), capture_output=True, text=True,
                            timeout=600)
         assert 'IDX_DUMP_OK' in r.stdout, r.stderr[-3000:]
         outs[flag] = torch.load(path)

@@ -5,6 +5,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from guard import guard_allocations  # noqa: F401  (autouse: poisoned, guard-banded allocations)
 from util import DEV, close, rnd, to_act
 
 pytestmark = pytest.mark.gpu
@@ -729,7 +730,7 @@ for cin, cout, k in ((64, 64, (1, 3)), (256, 128, (3, 1)), (128, 40, (3, 3))):
     worst = max(worst, errw)
 print("BF16_OK %.2e" % worst)
 '''
-    env = dict(os.environ, EMSA_BF16_MFMA='1')
+    env = dict(os.environ, EMSA_BF16_MFMA='1', EMSA_POISON='1')
     r = subprocess.run([sys.executable, '-c', code], cwd=root, env=env, capture_output=True,
                        text=True, timeout=300)
     assert 'BF16_OK' in r.stdout, r.stderr[-2000:]
@@ -884,7 +885,7 @@ err = (dw.cpu().double() - wt.grad).abs().max().item() / wt.grad.abs().max().ite
 assert err < 2e-4, err
 print("INBN_BF16_OK %.2e" % err)
 '''
-    env = dict(os.environ, EMSA_BF16_MFMA='1')
+    env = dict(os.environ, EMSA_BF16_MFMA='1', EMSA_POISON='1')
     r = subprocess.run([sys.executable, '-c', code], cwd=root, env=env, capture_output=True,
                        text=True, timeout=300)
     assert 'INBN_BF16_OK' in r.stdout, r.stderr[-2000:]

@@ -15,6 +15,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import postprocessing_cases as C   # noqa: E402
+from guard import guard_allocations  # noqa: E402,F401  (autouse: poisoned, guard-banded allocations)
 from oracle import postprocessing_oracle as O   # noqa: E402
 
 pytestmark = pytest.mark.gpu

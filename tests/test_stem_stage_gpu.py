@@ -13,6 +13,7 @@ import math
 import pytest
 import torch
 
+from guard import guard_allocations  # noqa: F401  (autouse: poisoned, guard-banded allocations)
 from util import DEV, rnd, to_act
 
 pytestmark = pytest.mark.gpu
