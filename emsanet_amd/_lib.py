@@ -90,6 +90,12 @@ SIGNATURES = {
     'emsa_dropout2d_mask_batch': (c_int, [_P, _P, c_int32, c_int32, c_int32, c_uint32, _P, _P]),
     'emsa_to_nhwc_t': (c_int, [c_int32, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int64, c_int64,
                                c_int64, c_int64, _P]),
+    'emsa_conv1d_wino_resmask_supported': (c_int, [_GP, c_int32]),
+    'emsa_conv1d_wino_resmask': (c_int, [_GP, _P, _P, _P, _P, c_int32, _P, _P]),
+    'emsa_bn_act_fwd_wbits': (c_int, [_P, _P, _P, _P, _P, _P, c_int32, c_int64, c_int32, c_int32, _P, _P]),
+    'emsa_bn_act_fwd_raff': (c_int, [_P] * 8 + [c_int32, c_int64, c_int32, c_int32, _P, c_int32, _P]),
+    'emsa_bn_bwd_reduce_wbits': (c_int, [_P, _P, _P, _P, _P, _P, c_int32, c_int64, c_int32, _P, _P]),
+    'emsa_bn_bwd_apply_wbits': (c_int, [_P] * 8 + [c_int32, c_int32, c_int64, c_int32, c_int32] + [_P] * 5),
     'emsa_conv1d_wino_inbn': (c_int, [_GP, _P, _P, _P, _P, _P, _P, _P, c_int32, _P, _P]),
     'emsa_conv_wgrad_inbn': (c_int, [_GP, _P, _P, _P, _P, _P, _P, _P, _P]),
     'emsa_conv_wgrad_inbn_t': (c_int, [c_int32, _GP, _P, _P, _P, _P, _P, _P, _P, _P]),
@@ -146,6 +152,7 @@ SIGNATURES = {
     'emsa_se_scale_bwd_reduce': (c_int, [_P, _P, _P, _P, c_int32, c_int64, c_int32, _P]),
     'emsa_se_scale_bwd_apply': (c_int, [_P] * 5 + [c_int32, c_int64, c_int32, _P]),
     'emsa_up2x_dw3x3_fwd': (c_int, [_P] * 5 + [c_int32] * 4 + [_P]),
+    'emsa_up2x_dw3x3_fwd_skipbn': (c_int, [_P] * 7 + [c_int32] * 4 + [_P]),
     'emsa_up2x_dw3x3_bwd_data': (c_int, [_P] * 3 + [c_int32] * 4 + [_P]),
     'emsa_up2x_dw3x3_bwd_weight': (c_int, [_P] * 4 + [c_int32] * 4 + [_P]),
     'emsa_up2x_dw3x3_bwd': (c_int, [_P] * 6 + [c_int32] * 4 + [_P]),

@@ -60,6 +60,9 @@ struct WinoArgs {
   const float* residual;
   const float* mask_src;
   const uint64_t* mask_bits;        // alternative to mask_src: 1 bit per element, see relu_bits
+  int mask_res;                     // 1: mask_bits gates the RESIDUAL only, v = acc + (bit ? residual : 0)
+                                    // (emsa_conv1d_wino_resmask: the residual is a gradient whose ReLU
+                                    // mask was never applied in memory)
   uint64_t* relu_bits;              // out: (result > 0), one word per (pixel, 64-channel tile):
                                     // bit = component*16 + float4 column
   // BatchNorm-backward sums fused into a data gradient (emsa_conv1d_wino_bnb): the result dz is the
@@ -502,9 +505,22 @@ __global__ __launch_bounds__(256, kWN == 64 ? (BNB ? 4 : 5) : 6) void conv1d_win
         vlo = __builtin_elementwise_fma(vlo, sclo, shlo);
         vhi = __builtin_elementwise_fma(vhi, schi, shhi);
       }
+      // ReLU masks as bits: the 16 lanes that share a pixel share one 64-bit word; bit
+      // comp * 16 + col4 -> x, y in the low word, z, w in the high word
+      auto gate = [&](float4& q) {
+        const uint32_t t0 = rbits[k].x >> col4, t1 = rbits[k].y >> col4;
+        q.x = __uint_as_float(__float_as_uint(q.x) & (uint32_t)__builtin_amdgcn_sbfe((int)t0, 0, 1));
+        q.y = __uint_as_float(__float_as_uint(q.y) & (uint32_t)__builtin_amdgcn_sbfe((int)t0, 16, 1));
+        q.z = __uint_as_float(__float_as_uint(q.z) & (uint32_t)__builtin_amdgcn_sbfe((int)t1, 0, 1));
+        q.w = __uint_as_float(__float_as_uint(q.w) & (uint32_t)__builtin_amdgcn_sbfe((int)t1, 16, 1));
+      };
       if (p.residual) {
-        vlo += wf32x2{rres[k].x, rres[k].y};
-        vhi += wf32x2{rres[k].z, rres[k].w};
+        float4 rr = rres[k];
+        if constexpr (kWN == 64) {
+          if (p.mask_res) gate(rr);
+        }
+        vlo += wf32x2{rr.x, rr.y};
+        vhi += wf32x2{rr.z, rr.w};
       }
       float4 v = make_float4(vlo.x, vlo.y, vhi.x, vhi.y);
       if constexpr (bnb) {
@@ -525,15 +541,7 @@ __global__ __launch_bounds__(256, kWN == 64 ? (BNB ? 4 : 5) : 6) void conv1d_win
         v.z = mm.z > 0.f ? v.z : 0.f; v.w = mm.w > 0.f ? v.w : 0.f;
       }
       if constexpr (kWN == 64) {
-        // ReLU masks as bits: the 16 lanes that share a pixel share one 64-bit word; bit
-        // comp * 16 + col4 -> x, y in the low word, z, w in the high word
-        if (p.mask_bits) {
-          const uint32_t t0 = rbits[k].x >> col4, t1 = rbits[k].y >> col4;
-          v.x = __uint_as_float(__float_as_uint(v.x) & (uint32_t)__builtin_amdgcn_sbfe((int)t0, 0, 1));
-          v.y = __uint_as_float(__float_as_uint(v.y) & (uint32_t)__builtin_amdgcn_sbfe((int)t0, 16, 1));
-          v.z = __uint_as_float(__float_as_uint(v.z) & (uint32_t)__builtin_amdgcn_sbfe((int)t1, 0, 1));
-          v.w = __uint_as_float(__float_as_uint(v.w) & (uint32_t)__builtin_amdgcn_sbfe((int)t1, 16, 1));
-        }
+        if (p.mask_bits && !p.mask_res) gate(v);
       }
       if (p.act == EMSA_ACT_RELU) {
         v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f);
@@ -852,6 +860,15 @@ extern "C" int emsa_conv1d_wino_stats_rows(const EmsaConvGeom* g) {
   return (int)((mp + kPairs - 1) / kPairs);
 }
 
+// channel-tile width: EMSA_WINO_WN=32|64 forces it (tuning)
+static int wino_wn() {
+  static const int forced_wn = [] {
+    const char* e = getenv("EMSA_WINO_WN");
+    return e ? atoi(e) : 0;
+  }();
+  return forced_wn == 32 || forced_wn == 64 ? forced_wn : 64;
+}
+
 static int conv1d_wino_impl(const EmsaConvGeom* g, const float* in, const float* u, float* out,
                             const float* bias, float* stats, const float* scale,
                             const float* shift, const float* residual, int32_t ld_res,
@@ -859,7 +876,7 @@ static int conv1d_wino_impl(const EmsaConvGeom* g, const float* in, const float*
                             const uint64_t* mask_bits, uint64_t* relu_bits,
                             const float* bnb_mean, const float* bnb_invstd, float* bnb_out,
                             int32_t bnb_rows_alloc, const float* in_scale, const float* in_shift,
-                            void* stream) {
+                            void* stream, bool mask_res = false) {
   if (!emsa_conv1d_wino_supported(g)) return EMSA_E_SHAPE;
   if ((in_scale == nullptr) != (in_shift == nullptr)) return EMSA_E_ARG;
   if (!in || !u || !out) return EMSA_E_ARG;
@@ -873,6 +890,7 @@ static int conv1d_wino_impl(const EmsaConvGeom* g, const float* in, const float*
   a.in = in; a.u = u; a.out = out; a.bias = bias; a.stats = stats; a.scale = scale;
   a.shift = shift; a.residual = residual; a.mask_src = mask_src;
   a.mask_bits = mask_bits; a.relu_bits = relu_bits;
+  a.mask_res = mask_res ? 1 : 0;
   a.bnb_mean = bnb_mean; a.bnb_invstd = bnb_invstd; a.bnb_out = bnb_out;
   a.bnb_rows_alloc = bnb_rows_alloc;
   a.in_scale = in_scale; a.in_shift = in_shift;
@@ -892,14 +910,10 @@ static int conv1d_wino_impl(const EmsaConvGeom* g, const float* in, const float*
   a.px_simg = H * W;
   a.px_sa = aw ? W : 1;
   a.px_sb = aw ? 1 : W;
-  // channel-tile width: EMSA_WINO_WN=32|64 forces it (tuning)
-  static const int forced_wn = [] {
-    const char* e = getenv("EMSA_WINO_WN");
-    return e ? atoi(e) : 0;
-  }();
-  const int wn = forced_wn == 32 || forced_wn == 64 ? forced_wn : 64;
+  const int wn = wino_wn();
   if ((mask_bits || relu_bits) && wn != 64) return EMSA_E_SHAPE;
   if (mask_bits && mask_src) return EMSA_E_ARG;
+  if (mask_res && (!mask_bits || !residual || bnb_out || relu_bits || in_scale)) return EMSA_E_ARG;
   a.tiles_m = (a.MP + kPairs - 1) / kPairs;
   a.tiles_n = (g->n_ch + wn - 1) / wn;
   if (bnb_out) {
@@ -965,6 +979,28 @@ extern "C" int emsa_conv1d_wino(const EmsaConvGeom* g, const float* in, const fl
   return conv1d_wino_impl(g, in, u, out, bias, stats, scale, shift, residual, ld_res, mask_src,
                           ld_mask, act, mask_bits, relu_bits, nullptr, nullptr, nullptr, 0, nullptr,
                           nullptr, stream);
+}
+
+// Data gradient whose residual operand arrives UNMASKED with its ReLU mask beside it as bits:
+// out = conv_transpose(dy) + (bit ? residual : 0).  res_bits = one 64-bit word per (pixel, 64-channel
+// tile of the output), bit comp * 16 + col4 -- the layout of relu_bits, which emsa_bn_act_fwd_wbits
+// writes for a BatchNorm output.  The masked residual (an NBt1D block's skip gradient) is never stored.
+// emsa_conv1d_wino_resmask_supported: 1 where this launch takes the geometry (host-side, no launch).
+extern "C" int emsa_conv1d_wino_resmask_supported(const EmsaConvGeom* g, int32_t ld_res) {
+  if (!emsa_conv1d_wino_supported(g) || wino_wn() != 64) return 0;
+  if ((g->n_ch & 63) || ld_res < g->n_ch || (ld_res & 3)) return 0;
+  const long px = (long)g->n_img * g->out_h * g->out_w, lim = 1L << 29;
+  if (px * g->ld_out >= lim || px * ld_res >= lim || px * (g->n_ch / 64) * 2 >= lim) return 0;
+  return 1;
+}
+extern "C" int emsa_conv1d_wino_resmask(const EmsaConvGeom* g, const float* dy, const float* u,
+                                        float* out, const float* residual, int32_t ld_res,
+                                        const uint64_t* res_bits, void* stream) {
+  if (!residual || !res_bits) return EMSA_E_ARG;
+  if (!emsa_conv1d_wino_resmask_supported(g, ld_res)) return EMSA_E_SHAPE;
+  return conv1d_wino_impl(g, dy, u, out, nullptr, nullptr, nullptr, nullptr, residual, ld_res, nullptr,
+                          0, EMSA_ACT_NONE, res_bits, nullptr, nullptr, nullptr, nullptr, 0, nullptr,
+                          nullptr, stream, true);
 }
 
 // Forward 1-D conv of a = relu(in * in_scale[c] + in_shift[c]) (per INPUT channel, c_in floats

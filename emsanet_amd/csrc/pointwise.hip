@@ -385,12 +385,34 @@ __device__ __forceinline__ void ldf(const float* p, float (&v)[V]) {       // V 
 // per element for the backward pass (which otherwise re-reads y only for this): the wave's 64
 // vector indices [i & ~63, +64) -> V words, one per component; lanes past the end are inactive and
 // contribute 0 bits
+// wbits (fp32, c % 64 == 0; emsa_bn_act_fwd_wbits): the same bits in the layout the Winograd
+// epilogue reads (conv_wino.hip relu_bits / mask_bits): one word per (pixel, 64-channel tile) = per 16
+// consecutive vector indices, word i >> 4, bit comp * 16 + (i & 15).  The word count is the same.
+template <int V>
+__device__ __forceinline__ void relu_bits_store(uint64_t* __restrict__ mask_bits, uint64_t idx,
+                                                const uint64_t (&b)[V], int wbits) {
+  if (wbits) {
+    if constexpr (V == 4) {
+      if ((idx & 15) == 0) {
+        const int sh = (int)(idx & 48);              // this word's 16 lanes within the wave
+        mask_bits[idx >> 4] = ((b[0] >> sh) & 0xFFFFull) | (((b[1] >> sh) & 0xFFFFull) << 16) |
+                              (((b[2] >> sh) & 0xFFFFull) << 32) | (((b[3] >> sh) & 0xFFFFull) << 48);
+      }
+    }
+  } else if ((idx & 63) == 0) {
+    uint64_t* m = mask_bits + (idx >> 6) * V;
+#pragma unroll
+    for (int k = 0; k < V; ++k) m[k] = b[k];
+  }
+}
 template <typename T>
 __global__ void bn_act_fwd_kernel(const T* __restrict__ x, T* __restrict__ y,
                                   const float* __restrict__ scale, const float* __restrict__ shift,
                                   const float* __restrict__ drop,
                                   const T* __restrict__ residual, long hw, int cvn, long totalv,
-                                  int act, uint64_t* __restrict__ mask_bits) {
+                                  int act, uint64_t* __restrict__ mask_bits, int wbits = 0,
+                                  const float* __restrict__ res_scale = nullptr,
+                                  const float* __restrict__ res_shift = nullptr) {
   constexpr int V = VecIO<T>::V;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < totalv;
        i += (long)gridDim.x * blockDim.x) {
@@ -411,6 +433,13 @@ __global__ void bn_act_fwd_kernel(const T* __restrict__ x, T* __restrict__ y,
     if (residual) {
       float r[V];
       VecIO<T>::load(residual + i * V, r);
+      if (res_scale) {                               // the residual is bn_affine(residual): see RAFF below
+        float rsc[V], rsh[V];
+        ldf<V>(res_scale + cv * V, rsc);
+        ldf<V>(res_shift + cv * V, rsh);
+#pragma unroll
+        for (int k = 0; k < V; ++k) r[k] = bn_affine(r[k], rsc[k], rsh[k]);
+      }
 #pragma unroll
       for (int k = 0; k < V; ++k) v[k] = bn_add(v[k], r[k]);
     }
@@ -423,11 +452,7 @@ __global__ void bn_act_fwd_kernel(const T* __restrict__ x, T* __restrict__ y,
       uint64_t b[V];
 #pragma unroll
       for (int k = 0; k < V; ++k) b[k] = __ballot(v[k] > 0.f);
-      if ((i & 63) == 0) {
-        uint64_t* m = mask_bits + (i >> 6) * V;
-#pragma unroll
-        for (int k = 0; k < V; ++k) m[k] = b[k];
-      }
+      relu_bits_store<V>(mask_bits, (uint64_t)i, b, wbits);
     }
   }
 }
@@ -446,11 +471,18 @@ __global__ void bn_act_fwd_kernel(const T* __restrict__ x, T* __restrict__ y,
 //   * the same arithmetic in the same order (bn_affine / bn_mul / bn_dx_train ...: every fma spelled
 //     out): results are bit-identical to the loops above, which stay as the general form
 //     (EMSA_BN_FAST=0 selects them for A/B runs; tests/test_ops16_gpu.py compares the two).
-template <typename T, bool DROP, bool RES>
+// RAFF (fp32, emsa_bn_act_fwd_raff): the residual operand is itself the output of a BatchNorm without
+// activation, residual * res_scale[c] + res_shift[c] -- the down-sampling shortcut bnds(conv1x1(x)) of
+// an NBt1D block -- formed here with the fma bn_act_fwd would have stored: that pass and its tensor
+// disappear, the sum is bit-identical.
+template <typename T, bool DROP, bool RES, bool RAFF = false>
 __global__ __launch_bounds__(kThreads) void bn_act_fwd_fast_kernel(
     const T* __restrict__ x, T* __restrict__ y, const float* __restrict__ scale,
     const float* __restrict__ shift, const float* __restrict__ drop, const T* __restrict__ residual,
-    uint32_t hw, int cvn_log2, uint32_t totalv, int act, uint64_t* __restrict__ mask_bits) {
+    uint32_t hw, int cvn_log2, uint32_t totalv, int act, uint64_t* __restrict__ mask_bits,
+    int wbits = 0, const float* __restrict__ res_scale = nullptr,
+    const float* __restrict__ res_shift = nullptr) {
+  static_assert(!RAFF || RES, "RAFF: an affine map of the residual operand");
   constexpr int V = VecIO<T>::V;
   typedef typename VecIO<T>::raw Raw;
   const uint32_t stride = gridDim.x * kThreads;
@@ -461,6 +493,11 @@ __global__ __launch_bounds__(kThreads) void bn_act_fwd_fast_kernel(
   float sc[V], sh[V];
   ldf<V>(scale + cv * V, sc);
   ldf<V>(shift + cv * V, sh);
+  [[maybe_unused]] float rsc[V], rsh[V];
+  if constexpr (RAFF) {
+    ldf<V>(res_scale + cv * V, rsc);
+    ldf<V>(res_shift + cv * V, rsh);
+  }
   auto finish = [&](uint32_t idx, const Raw& rx, const Raw& rr, const float (&d)[V]) {
     float v[V];
     VecIO<T>::cvt(rx, v);
@@ -473,6 +510,10 @@ __global__ __launch_bounds__(kThreads) void bn_act_fwd_fast_kernel(
     if constexpr (RES) {
       float r[V];
       VecIO<T>::cvt(rr, r);
+      if constexpr (RAFF) {
+#pragma unroll
+        for (int k = 0; k < V; ++k) r[k] = bn_affine(r[k], rsc[k], rsh[k]);
+      }
 #pragma unroll
       for (int k = 0; k < V; ++k) v[k] = bn_add(v[k], r[k]);
     }
@@ -485,11 +526,7 @@ __global__ __launch_bounds__(kThreads) void bn_act_fwd_fast_kernel(
       uint64_t b[V];
 #pragma unroll
       for (int k = 0; k < V; ++k) b[k] = __ballot(v[k] > 0.f);
-      if ((idx & 63) == 0) {
-        uint64_t* m = mask_bits + (size_t)(idx >> 6) * V;
-#pragma unroll
-        for (int k = 0; k < V; ++k) m[k] = b[k];
-      }
+      relu_bits_store<V>(mask_bits, (uint64_t)idx, b, wbits);
     }
   };
   auto ld_drop = [&](uint32_t px, float (&d)[V]) {
@@ -526,7 +563,14 @@ __global__ __launch_bounds__(kThreads) void bn_act_fwd_fast_kernel(
 
 // (y > 0) of vector index i from the bit mask written by bn_act_fwd_kernel
 template <int V>
-__device__ __forceinline__ void relu_maskv(const uint64_t* __restrict__ bits, long i, bool (&m)[V]) {
+__device__ __forceinline__ void relu_maskv(const uint64_t* __restrict__ bits, long i, bool (&m)[V],
+                                           int wbits = 0) {
+  if (wbits) {                                       // (relu_bits_store: word i >> 4, bit k * 16 + (i & 15))
+    const uint64_t w = bits[i >> 4] >> (int)(i & 15);
+#pragma unroll
+    for (int k = 0; k < V; ++k) m[k] = (w >> ((16 * k) & 63)) & 1ull;
+    return;
+  }
   const uint64_t* w = bits + (i >> 6) * V;
   const int sh = (int)(i & 63);
 #pragma unroll
@@ -573,12 +617,12 @@ __device__ __forceinline__ void bn_bwd_load(const T* __restrict__ dy, const T* _
                                             const uint64_t* __restrict__ mask_bits,
                                             const float* __restrict__ drop, long i, long pix,
                                             long hw, int cvn, int cv, int act, float (&g)[V],
-                                            float (&gres)[V]) {
+                                            float (&gres)[V], int wbits = 0) {
   VecIO<T>::load(dy + i * V, g);
   if (act == EMSA_ACT_RELU) {
     if (mask_bits) {
       bool m[V];
-      relu_maskv<V>(mask_bits, i, m);
+      relu_maskv<V>(mask_bits, i, m, wbits);
 #pragma unroll
       for (int k = 0; k < V; ++k) g[k] = m[k] ? g[k] : 0.f;
     } else {
@@ -606,7 +650,8 @@ __global__ void bn_bwd_reduce_kernel(const T* __restrict__ dy, const T* __restri
                                      const T* __restrict__ x, const float* __restrict__ mean,
                                      const float* __restrict__ invstd,
                                      const float* __restrict__ drop, long pixels, long hw, int cvn,
-                                     int act, int rows_alloc, float* __restrict__ partial) {
+                                     int act, int rows_alloc, float* __restrict__ partial,
+                                     int wbits = 0) {
   constexpr int V = VecIO<T>::V;
   extern __shared__ __attribute__((aligned(16))) float cred[];   // [2][lanes][c]
   const int rows = gridDim.x;
@@ -624,7 +669,7 @@ __global__ void bn_bwd_reduce_kernel(const T* __restrict__ dy, const T* __restri
     for (long p = p0 + rl; p < p1; p += lanes) {
       const long i = p * cvn + cv;
       float g[V], gres[V], xx[V];
-      bn_bwd_load<T, V>(dy, y, mask_bits, drop, i, p, hw, cvn, cv, act, g, gres);
+      bn_bwd_load<T, V>(dy, y, mask_bits, drop, i, p, hw, cvn, cv, act, g, gres, wbits);
       VecIO<T>::load(x + i * V, xx);
 #pragma unroll
       for (int k = 0; k < V; ++k) {
@@ -657,7 +702,7 @@ __global__ void bn_bwd_reduce_wide_kernel(const T* __restrict__ dy, const T* __r
                                           const float* __restrict__ invstd,
                                           const float* __restrict__ drop, long pixels, long hw,
                                           int cvn, int act, int rows_alloc,
-                                          float* __restrict__ partial) {
+                                          float* __restrict__ partial, int wbits = 0) {
   constexpr int V = VecIO<T>::V;
   const int cv = blockIdx.y * kThreads + threadIdx.x;
   if (cv >= cvn) return;
@@ -672,7 +717,7 @@ __global__ void bn_bwd_reduce_wide_kernel(const T* __restrict__ dy, const T* __r
   for (long p = p0; p < p1; ++p) {
     const long i = p * cvn + cv;
     float g[V], gres[V], xx[V];
-    bn_bwd_load<T, V>(dy, y, mask_bits, drop, i, p, hw, cvn, cv, act, g, gres);
+    bn_bwd_load<T, V>(dy, y, mask_bits, drop, i, p, hw, cvn, cv, act, g, gres, wbits);
     VecIO<T>::load(x + i * V, xx);
 #pragma unroll
     for (int k = 0; k < V; ++k) {
@@ -731,7 +776,7 @@ __global__ void bn_bwd_apply_kernel(const T* __restrict__ dy, const T* __restric
                                     int rows_alloc, float* __restrict__ dbeta_out,
                                     float* __restrict__ dgamma_out, long hw, int cvn,
                                     long totalv, float inv_count, int act, int train,
-                                    T* __restrict__ dx, T* __restrict__ dres) {
+                                    T* __restrict__ dx, T* __restrict__ dres, int wbits = 0) {
   constexpr int V = VecIO<T>::V;
   // level 2 of the (sum dy, sum dy*xhat) reduction: merge the slice sums of bn_bwd_sum_kernel
   extern __shared__ __attribute__((aligned(16))) float sums[];   // [2][c]
@@ -758,7 +803,7 @@ __global__ void bn_bwd_apply_kernel(const T* __restrict__ dy, const T* __restric
     const int cv = (int)(i % cvn);
     const long pix = i / cvn;
     float g[V], gres[V], o[V], ga[V], is[V];
-    bn_bwd_load<T, V>(dy, y, mask_bits, drop, i, pix, hw, cvn, cv, act, g, gres);
+    bn_bwd_load<T, V>(dy, y, mask_bits, drop, i, pix, hw, cvn, cv, act, g, gres, wbits);
     if (dres) VecIO<T>::store(dres + i * V, gres);
     ldf<V>(gamma + cv * V, ga);
     ldf<V>(invstd + cv * V, is);
@@ -781,11 +826,13 @@ __global__ void bn_bwd_apply_kernel(const T* __restrict__ dy, const T* __restric
 
 // fast form of bn_bwd_reduce_kernel (see bn_act_fwd_fast_kernel): same thread -> (pixel lane,
 // channel vector) mapping and the same summation order, i.e. bit-identical partial rows; MASK = 0
-// none / 1 the bit mask / 2 the activation output y
+// none / 1 the bit mask / 2 the activation output y / 4 the bit mask in the Winograd epilogue's layout
+// (relu_bits_store with wbits: ONE word per 16 vector indices, 8 bytes per thread instead of 32)
 template <typename T, int MASK, bool DROP>
 struct BnBwdElem {
   typename VecIO<T>::raw g, x, y;
   ulonglong2 w[VecIO<T>::V / 2];
+  uint64_t wb;
   float d[VecIO<T>::V];
 };
 template <typename T, int MASK, bool DROP>
@@ -804,6 +851,7 @@ __device__ __forceinline__ void bn_bwd_issue(BnBwdElem<T, MASK, DROP>& e, const 
     for (int k = 0; k < V / 2; ++k) e.w[k] = w[k];
   }
   if constexpr (MASK == 2) e.y = VecIO<T>::load_raw(y + (size_t)i * V);
+  if constexpr (MASK == 4) e.wb = mask_bits[i >> 4];
   if constexpr (DROP) ldf<V>(drop + ((size_t)(pix / hw) * cvn + cv) * V, e.d);
 }
 // -> g (masked, dropped), gres (masked): the values bn_bwd_load produces
@@ -835,6 +883,12 @@ __device__ __forceinline__ void bn_bwd_grad(const BnBwdElem<T, MASK, DROP>& e, u
     VecIO<T>::cvt(e.y, yy);
 #pragma unroll
     for (int k = 0; k < V; ++k) g[k] = yy[k] > 0.f ? g[k] : 0.f;
+  }
+  if constexpr (MASK == 4) {
+    static_assert(MASK != 4 || V == 4, "Winograd-layout bits: fp32 vectors");
+    const uint64_t w = e.wb >> (int)(i & 15);
+#pragma unroll
+    for (int k = 0; k < V; ++k) g[k] = ((w >> ((16 * k) & 63)) & 1ull) ? g[k] : 0.f;
   }
 #pragma unroll
   for (int k = 0; k < V; ++k) gres[k] = g[k];
@@ -1583,7 +1637,11 @@ __device__ __forceinline__ float4 dw_weight4(const float* __restrict__ w, int c,
 //  at CLAMPED coordinates, zeroed by a select, and the four skip values -- is issued before the first
 //  is used.  The border tests used to be branches around the loads: nine `s_waitcnt vmcnt(0)` in a row,
 //  then four more behind the stores -- 13 serialised memory round trips per thread and iteration.)
-template <typename T, typename TO, bool NT = false, typename I = long, bool SKIP = false>
+// SKBN (fp32 training, Fn.skip_fold): `skip` is the INPUT of the skip path's BatchNorm and the value
+// added is relu(skip * sk_scale[c] + sk_shift[c]) -- bn_affine and fmaxf, what bn_act_fwd stores, so
+// the sum is bit-identical to the one over the stored activation; scale / shift sit behind the
+// weights in LDS ([2][c]), the four skip loads are issued where they were.
+template <typename T, typename TO, bool NT = false, typename I = long, bool SKIP = false, bool SKBN = false>
 __global__ __launch_bounds__(kThreads) void up2x_dw_fwd_kernel(const T* __restrict__ x, const float* __restrict__ wdw,
                                    const float* __restrict__ bias, const T* __restrict__ skip,
                                    TO* __restrict__ y, int n, int h, int w, int c4n,
@@ -1591,7 +1649,10 @@ __global__ __launch_bounds__(kThreads) void up2x_dw_fwd_kernel(const T* __restri
                                    const float* __restrict__ wdw2 = nullptr,
                                    const float* __restrict__ bias2 = nullptr,
                                    const T* __restrict__ skip2 = nullptr,
-                                   TO* __restrict__ y2 = nullptr) {
+                                   TO* __restrict__ y2 = nullptr,
+                                   const float* __restrict__ sk_scale = nullptr,
+                                   const float* __restrict__ sk_shift = nullptr) {
+  static_assert(!SKBN || (SKIP && std::is_same<T, float>::value), "SKBN: fp32 skip tensors");
   // twin launch (emsa_up2x_dw3x3_fwd_pair_t, grid.y = 2): the second half of the workgroups runs the
   // same shape on the "2" tensors (the other decoder of the model)
   if (blockIdx.y != 0) {
@@ -1602,6 +1663,12 @@ __global__ __launch_bounds__(kThreads) void up2x_dw_fwd_kernel(const T* __restri
   extern __shared__ __attribute__((aligned(16))) float wl[];
   const int C = c4n * 4;
   for (int j = threadIdx.x; j < 9 * C; j += blockDim.x) wl[(j % 9) * C + j / 9] = wdw[j];
+  if constexpr (SKBN) {
+    for (int j = threadIdx.x; j < C; j += blockDim.x) {
+      wl[9 * C + j] = sk_scale[j];
+      wl[10 * C + j] = sk_shift[j];
+    }
+  }
   __syncthreads();
   const I total = (I)n * h * w * c4n;
   const int ow_n = 2 * w;
@@ -1642,6 +1709,17 @@ __global__ __launch_bounds__(kThreads) void up2x_dw_fwd_kernel(const T* __restri
 #pragma unroll
     for (int t = 0; t < 9; ++t) k[t] = emsa_ld4(wl + t * C + c4 * 4);
     const float4 bv = bias ? emsa_ld4(bias + c4 * 4) : emsa_zero4();
+    if constexpr (SKBN) {
+      const float4 sc = emsa_ld4(wl + 9 * C + c4 * 4), sh = emsa_ld4(wl + 10 * C + c4 * 4);
+#pragma unroll
+      for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+          float4& s = sk[a][b];
+          s.x = fmaxf(bn_affine(s.x, sc.x, sh.x), 0.f); s.y = fmaxf(bn_affine(s.y, sc.y, sh.y), 0.f);
+          s.z = fmaxf(bn_affine(s.z, sc.z, sh.z), 0.f); s.w = fmaxf(bn_affine(s.w, sc.w, sh.w), 0.f);
+        }
+    }
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -2851,11 +2929,18 @@ static int bn_fast_log2(int cvn, long totalv, long hw) {
 }
 // channel count admissible for the vectorised BatchNorm passes of storage type T
 template <typename T> static bool cv_ok(int c) { return c4_ok(c) && c % VecIO<T>::V == 0; }
+// ... and for the ReLU bit mask in the Winograd epilogue's layout (relu_bits_store): fp32 storage,
+// whole 64-channel tiles
+template <typename T> static bool wbits_ok(int c) { return std::is_same<T, float>::value && c % 64 == 0; }
 
 template <typename T>
-static int bn_act_fwd_impl(const T* x, T* y, const float* scale, const float* shift, const float* drop, const T* residual, int32_t n_img, int64_t hw, int32_t c, int32_t act, uint64_t* mask_bits, void* stream) {
+static int bn_act_fwd_impl(const T* x, T* y, const float* scale, const float* shift, const float* drop, const T* residual, int32_t n_img, int64_t hw, int32_t c, int32_t act, uint64_t* mask_bits, void* stream, int wbits = 0, const float* res_scale = nullptr, const float* res_shift = nullptr) {
   if (!x || !y || !scale || !shift) return EMSA_E_ARG;
+  if ((res_scale == nullptr) != (res_shift == nullptr) || (res_scale && !residual)) return EMSA_E_ARG;
+  if (res_scale && !std::is_same<T, float>::value) return EMSA_E_SHAPE;
   if (!cv_ok<T>(c)) return EMSA_E_SHAPE;
+  if (wbits && !wbits_ok<T>(c)) return EMSA_E_SHAPE;
+  if (wbits && (!mask_bits || act != EMSA_ACT_RELU)) return EMSA_E_ARG;
   constexpr int V = VecIO<T>::V;
   const long totalv = (long)n_img * hw * (c / V);
   const int lg = bn_fast_log2(c / V, totalv, hw);
@@ -2864,8 +2949,19 @@ static int bn_act_fwd_impl(const T* x, T* y, const float* scale, const float* sh
     hipStream_t st = (hipStream_t)stream;
 #define EMSA_FWD_FAST(D, R)                                                                        \
   hipLaunchKernelGGL((bn_act_fwd_fast_kernel<T, D, R>), grid, block, 0, st, x, y, scale, shift,   \
-                     drop, residual, (uint32_t)hw, lg, (uint32_t)totalv, act, mask_bits)
-    if (drop) {
+                     drop, residual, (uint32_t)hw, lg, (uint32_t)totalv, act, mask_bits, wbits)
+    if (res_scale) {
+      if constexpr (std::is_same<T, float>::value) {
+        if (drop)
+          hipLaunchKernelGGL((bn_act_fwd_fast_kernel<T, true, true, true>), grid, block, 0, st, x, y, scale,
+                             shift, drop, residual, (uint32_t)hw, lg, (uint32_t)totalv, act, mask_bits,
+                             wbits, res_scale, res_shift);
+        else
+          hipLaunchKernelGGL((bn_act_fwd_fast_kernel<T, false, true, true>), grid, block, 0, st, x, y, scale,
+                             shift, drop, residual, (uint32_t)hw, lg, (uint32_t)totalv, act, mask_bits,
+                             wbits, res_scale, res_shift);
+      }
+    } else if (drop) {
       if (residual) EMSA_FWD_FAST(true, true); else EMSA_FWD_FAST(true, false);
     } else {
       if (residual) EMSA_FWD_FAST(false, true); else EMSA_FWD_FAST(false, false);
@@ -2875,11 +2971,25 @@ static int bn_act_fwd_impl(const T* x, T* y, const float* scale, const float* sh
   }
   hipLaunchKernelGGL((bn_act_fwd_kernel<T>), dim3(grid_for(totalv)), dim3(kThreads), 0,
                      (hipStream_t)stream, x, y, scale, shift, drop, residual, (long)hw, c / V,
-                     totalv, act, mask_bits);
+                     totalv, act, mask_bits, wbits, res_scale, res_shift);
   return emsa_launch_status();
 }
 extern "C" int emsa_bn_act_fwd(const float* x, float* y, const float* scale, const float* shift, const float* drop, const float* residual, int32_t n_img, int64_t hw, int32_t c, int32_t act, uint64_t* mask_bits, void* stream) {
   return bn_act_fwd_impl<float>(x, y, scale, shift, drop, residual, n_img, hw, c, act, mask_bits, stream);
+}
+// emsa_bn_act_fwd with the ReLU bit mask written in the layout the Winograd epilogue reads
+// (emsa_conv1d_wino_resmask): one word per (pixel, 64-channel tile), bit comp * 16 + col4.  fp32,
+// c % 64 == 0, ReLU; emsa_relu_mask_words words as before.  Read by emsa_bn_bwd_*_wbits.
+extern "C" int emsa_bn_act_fwd_wbits(const float* x, float* y, const float* scale, const float* shift, const float* drop, const float* residual, int32_t n_img, int64_t hw, int32_t c, int32_t act, uint64_t* mask_bits, void* stream) {
+  return bn_act_fwd_impl<float>(x, y, scale, shift, drop, residual, n_img, hw, c, act, mask_bits, stream, 1);
+}
+// emsa_bn_act_fwd whose residual operand is the INPUT of another BatchNorm without activation (an
+// NBt1D block's down-sampling shortcut): y = act((x*scale + shift)*drop + (res_src*res_scale +
+// res_shift)), the inner map with the fma emsa_bn_act_fwd would have stored -- bit-identical to the two
+// passes.  wbits != 0: the mask in the layout of emsa_bn_act_fwd_wbits.  fp32.
+extern "C" int emsa_bn_act_fwd_raff(const float* x, float* y, const float* scale, const float* shift, const float* drop, const float* res_src, const float* res_scale, const float* res_shift, int32_t n_img, int64_t hw, int32_t c, int32_t act, uint64_t* mask_bits, int32_t wbits, void* stream) {
+  if (!res_src || !res_scale || !res_shift) return EMSA_E_ARG;
+  return bn_act_fwd_impl<float>(x, y, scale, shift, drop, res_src, n_img, hw, c, act, mask_bits, stream, wbits ? 1 : 0, res_scale, res_shift);
 }
 extern "C" int emsa_bn_act_fwd_t(int32_t dtype, const void* x, void* y, const float* scale, const float* shift, const float* drop, const void* residual, int32_t n_img, int64_t hw, int32_t c, int32_t act, uint64_t* mask_bits, void* stream) {
   switch (dtype) {
@@ -2911,11 +3021,13 @@ extern "C" int emsa_bn_bwd_rows(int64_t pixels, int32_t c) {
 }
 
 template <typename T>
-static int bn_bwd_reduce_impl(const T* dy, const T* y, const uint64_t* mask_bits, const T* x, const float* save_mean, const float* save_invstd, const float* drop, int32_t n_img, int64_t hw, int32_t c, int32_t act, float* partial, void* stream, const float* mask_scale = nullptr, const float* mask_shift = nullptr) {
+static int bn_bwd_reduce_impl(const T* dy, const T* y, const uint64_t* mask_bits, const T* x, const float* save_mean, const float* save_invstd, const float* drop, int32_t n_img, int64_t hw, int32_t c, int32_t act, float* partial, void* stream, const float* mask_scale = nullptr, const float* mask_shift = nullptr, int wbits = 0) {
   if (!dy || !x || !save_mean || !save_invstd || !partial) return EMSA_E_ARG;
   if (act == EMSA_ACT_RELU && !y && !mask_bits && !mask_scale) return EMSA_E_ARG;
   if ((mask_scale == nullptr) != (mask_shift == nullptr)) return EMSA_E_ARG;
   if (!cv_ok<T>(c)) return EMSA_E_SHAPE;
+  if (wbits && !wbits_ok<T>(c)) return EMSA_E_SHAPE;
+  if (wbits && (!mask_bits || mask_scale || act != EMSA_ACT_RELU)) return EMSA_E_ARG;
   const long pixels = (long)n_img * hw;
   const int rows = bn_bwd_rows_for(pixels, c);
   const int cvn = c / VecIO<T>::V, lanes = kThreads / cvn;
@@ -2923,7 +3035,7 @@ static int bn_bwd_reduce_impl(const T* dy, const T* y, const uint64_t* mask_bits
   if (bn_fast_on() && cvn <= kThreads && pixels * cvn < (1L << 31) && hw < (1L << 31)) {
     const dim3 grid(rows), block(kThreads);
     hipStream_t st = (hipStream_t)stream;
-    const int mask = act == EMSA_ACT_RELU ? (mask_scale ? 3 : mask_bits ? 1 : 2) : 0;
+    const int mask = act == EMSA_ACT_RELU ? (mask_scale ? 3 : mask_bits ? (wbits ? 4 : 1) : 2) : 0;
 #define EMSA_RED_FAST(M, D)                                                                        \
   hipLaunchKernelGGL((bn_bwd_reduce_fast_kernel<T, M, D>), grid, block, lds, st, dy, y, mask_bits, \
                      x, save_mean, save_invstd, drop, (uint32_t)pixels, (uint32_t)hw, cvn,        \
@@ -2931,6 +3043,10 @@ static int bn_bwd_reduce_impl(const T* dy, const T* y, const uint64_t* mask_bits
     if (mask == 3) {
       if (drop) return EMSA_E_ARG;
       EMSA_RED_FAST(3, false);
+    } else if (mask == 4) {
+      if constexpr (std::is_same<T, float>::value) {
+        if (drop) EMSA_RED_FAST(4, true); else EMSA_RED_FAST(4, false);
+      }
     } else if (drop) {
       if (mask == 1) EMSA_RED_FAST(1, true); else if (mask == 2) EMSA_RED_FAST(2, true); else EMSA_RED_FAST(0, true);
     } else {
@@ -2943,16 +3059,22 @@ static int bn_bwd_reduce_impl(const T* dy, const T* y, const uint64_t* mask_bits
   if (cvn > kThreads) {
     hipLaunchKernelGGL((bn_bwd_reduce_wide_kernel<T>), dim3(rows, (cvn + kThreads - 1) / kThreads),
                        dim3(kThreads), 0, (hipStream_t)stream, dy, y, mask_bits, x, save_mean,
-                       save_invstd, drop, pixels, (long)hw, cvn, act, rows + kBwdSlices, partial);
+                       save_invstd, drop, pixels, (long)hw, cvn, act, rows + kBwdSlices, partial, wbits);
     return emsa_launch_status();
   }
   hipLaunchKernelGGL((bn_bwd_reduce_kernel<T>), dim3(rows), dim3(kThreads), lds, (hipStream_t)stream,
                      dy, y, mask_bits, x, save_mean, save_invstd, drop, pixels, (long)hw, cvn, act,
-                     rows + kBwdSlices, partial);
+                     rows + kBwdSlices, partial, wbits);
   return emsa_launch_status();
 }
 extern "C" int emsa_bn_bwd_reduce(const float* dy, const float* y, const uint64_t* mask_bits, const float* x, const float* save_mean, const float* save_invstd, const float* drop, int32_t n_img, int64_t hw, int32_t c, int32_t act, float* partial, void* stream) {
   return bn_bwd_reduce_impl<float>(dy, y, mask_bits, x, save_mean, save_invstd, drop, n_img, hw, c, act, partial, stream);
+}
+// emsa_bn_bwd_reduce / emsa_bn_bwd_apply (ReLU) reading the bit mask emsa_bn_act_fwd_wbits wrote.
+// fp32, c % 64 == 0; the same partial rows, the same sums in the same order.
+extern "C" int emsa_bn_bwd_reduce_wbits(const float* dy, const uint64_t* mask_bits, const float* x, const float* save_mean, const float* save_invstd, const float* drop, int32_t n_img, int64_t hw, int32_t c, float* partial, void* stream) {
+  if (!mask_bits) return EMSA_E_ARG;
+  return bn_bwd_reduce_impl<float>(dy, nullptr, mask_bits, x, save_mean, save_invstd, drop, n_img, hw, c, EMSA_ACT_RELU, partial, stream, nullptr, nullptr, 1);
 }
 extern "C" int emsa_bn_bwd_reduce_t(int32_t dtype, const void* dy, const void* y, const uint64_t* mask_bits, const void* x, const float* save_mean, const float* save_invstd, const float* drop, int32_t n_img, int64_t hw, int32_t c, int32_t act, float* partial, void* stream) {
   switch (dtype) {
@@ -2964,12 +3086,14 @@ extern "C" int emsa_bn_bwd_reduce_t(int32_t dtype, const void* dy, const void* y
 }
 
 template <typename T>
-static int bn_bwd_apply_impl(const T* dy, const T* y, const uint64_t* mask_bits, const T* x, const float* gamma, const float* save_mean, const float* save_invstd, const float* drop, float* partial, int32_t rows_alloc, int32_t n_img, int64_t hw, int32_t c, int32_t act, int32_t train, T* dx, T* dres, float* dgamma, float* dbeta, void* stream, int32_t rows_given = -1, const float* mask_scale = nullptr, const float* mask_shift = nullptr) {
+static int bn_bwd_apply_impl(const T* dy, const T* y, const uint64_t* mask_bits, const T* x, const float* gamma, const float* save_mean, const float* save_invstd, const float* drop, float* partial, int32_t rows_alloc, int32_t n_img, int64_t hw, int32_t c, int32_t act, int32_t train, T* dx, T* dres, float* dgamma, float* dbeta, void* stream, int32_t rows_given = -1, const float* mask_scale = nullptr, const float* mask_shift = nullptr, int wbits = 0) {
   if (!dy || !x || !gamma || !save_mean || !save_invstd || !partial || !dx || !dgamma || !dbeta)
     return EMSA_E_ARG;
   if (act == EMSA_ACT_RELU && !y && !mask_bits && !mask_scale) return EMSA_E_ARG;
   if ((mask_scale == nullptr) != (mask_shift == nullptr)) return EMSA_E_ARG;
   if (!cv_ok<T>(c)) return EMSA_E_SHAPE;
+  if (wbits && !wbits_ok<T>(c)) return EMSA_E_SHAPE;
+  if (wbits && (!mask_bits || mask_scale || act != EMSA_ACT_RELU)) return EMSA_E_ARG;
   hipStream_t st = (hipStream_t)stream;
   const long pixels = (long)n_img * hw;
   // rows_given: the partial sums come from a convolution epilogue (one row per pixel tile of that
@@ -2992,7 +3116,7 @@ static int bn_bwd_apply_impl(const T* dy, const T* y, const uint64_t* mask_bits,
   if (lg >= 0) {
     const dim3 grid(ap_grid), block(kThreads);
     const size_t lds = (size_t)2 * c * sizeof(float);
-    const int mask = act == EMSA_ACT_RELU ? (mask_scale ? 3 : mask_bits ? 1 : 2) : 0;
+    const int mask = act == EMSA_ACT_RELU ? (mask_scale ? 3 : mask_bits ? (wbits ? 4 : 1) : 2) : 0;
     const float inv_count = 1.0f / (float)pixels;
 #define EMSA_APP_FAST(M, D, TR)                                                                     \
   hipLaunchKernelGGL((bn_bwd_apply_fast_kernel<T, M, D, TR>), grid, block, lds, st, dy, y,         \
@@ -3007,6 +3131,14 @@ static int bn_bwd_apply_impl(const T* dy, const T* y, const uint64_t* mask_bits,
     if (mask == 3) {
       if (drop || !train) return EMSA_E_ARG;      // (bn1 of an NBt1D block: batch statistics, no dropout)
       EMSA_APP_FAST(3, false, true);
+    } else if (mask == 4) {
+      if constexpr (std::is_same<T, float>::value) {
+        if (drop) {
+          if (train) EMSA_APP_FAST(4, true, true); else EMSA_APP_FAST(4, true, false);
+        } else {
+          if (train) EMSA_APP_FAST(4, false, true); else EMSA_APP_FAST(4, false, false);
+        }
+      }
     } else if (drop) {
       if (train) EMSA_APP_FAST_M(true, true); else EMSA_APP_FAST_M(true, false);
     } else {
@@ -3020,11 +3152,15 @@ static int bn_bwd_apply_impl(const T* dy, const T* y, const uint64_t* mask_bits,
   hipLaunchKernelGGL((bn_bwd_apply_kernel<T>), dim3(ap_grid), dim3(kThreads),
                      (size_t)2 * c * sizeof(float), st, dy, y, mask_bits, x, gamma, save_mean,
                      save_invstd, drop, partial, rows, rows_alloc, dbeta, dgamma, (long)hw, c / V, totalv,
-                     1.0f / (float)pixels, act, train, dx, dres);
+                     1.0f / (float)pixels, act, train, dx, dres, wbits);
   return emsa_launch_status();
 }
 extern "C" int emsa_bn_bwd_apply(const float* dy, const float* y, const uint64_t* mask_bits, const float* x, const float* gamma, const float* save_mean, const float* save_invstd, const float* drop, float* partial, int32_t rows_alloc, int32_t n_img, int64_t hw, int32_t c, int32_t act, int32_t train, float* dx, float* dres, float* dgamma, float* dbeta, void* stream) {
   return bn_bwd_apply_impl<float>(dy, y, mask_bits, x, gamma, save_mean, save_invstd, drop, partial, rows_alloc, n_img, hw, c, act, train, dx, dres, dgamma, dbeta, stream);
+}
+extern "C" int emsa_bn_bwd_apply_wbits(const float* dy, const uint64_t* mask_bits, const float* x, const float* gamma, const float* save_mean, const float* save_invstd, const float* drop, float* partial, int32_t rows_alloc, int32_t n_img, int64_t hw, int32_t c, int32_t train, float* dx, float* dres, float* dgamma, float* dbeta, void* stream) {
+  if (!mask_bits) return EMSA_E_ARG;
+  return bn_bwd_apply_impl<float>(dy, nullptr, mask_bits, x, gamma, save_mean, save_invstd, drop, partial, rows_alloc, n_img, hw, c, EMSA_ACT_RELU, train, dx, dres, dgamma, dbeta, stream, -1, nullptr, nullptr, 1);
 }
 extern "C" int emsa_bn_bwd_apply_t(int32_t dtype, const void* dy, const void* y, const uint64_t* mask_bits, const void* x, const float* gamma, const float* save_mean, const float* save_invstd, const float* drop, float* partial, int32_t rows_alloc, int32_t n_img, int64_t hw, int32_t c, int32_t act, int32_t train, void* dx, void* dres, float* dgamma, float* dbeta, void* stream) {
   switch (dtype) {
@@ -3398,19 +3534,22 @@ extern "C" int emsa_se_scale_bwd_apply_t(int32_t dtype, const void* dout, const 
   }
 }
 
+// non-temporal output stores for the wide fp32 maps: measured +4..10 % at 40 / 64 / 128 / 256
+// channels (c40 full resolution 659 -> 633 us), -20..-40 % at 8 channels (32-byte pixels)
+// (profiles/r03_d_pointwise_bench.txt); EMSA_UP2X_NT=0 / 1 forces it off / on
+static bool up2x_nt(int c) {
+  static const int nt_env = [] {
+    const char* e = getenv("EMSA_UP2X_NT");
+    return e ? (e[0] == '1' ? 1 : 0) : -1;
+  }();
+  return nt_env >= 0 ? nt_env == 1 : c >= 32;
+}
 template <typename T, typename TO>
 static int up2x_dw3x3_fwd_impl(const T* x, const float* wdw, const float* bias, const T* skip, TO* y, int32_t n, int32_t h, int32_t w, int32_t c, void* stream) {
   if (!x || !wdw || !y) return EMSA_E_ARG;
   if (!c4_ok(c)) return EMSA_E_SHAPE;
   const long total = (long)n * 4 * h * w * (c / 4);
-  // non-temporal output stores for the wide fp32 maps: measured +4..10 % at 40 / 64 / 128 / 256
-  // channels (c40 full resolution 659 -> 633 us), -20..-40 % at 8 channels (32-byte pixels)
-  // (profiles/r03_d_pointwise_bench.txt); EMSA_UP2X_NT=0 / 1 forces it off / on
-  static const int nt_env = [] {
-    const char* e = getenv("EMSA_UP2X_NT");
-    return e ? (e[0] == '1' ? 1 : 0) : -1;
-  }();
-  const bool nt = nt_env >= 0 ? nt_env == 1 : c >= 32;
+  const bool nt = up2x_nt(c);
   const dim3 grid(grid_for(total)), block(kThreads);
   const size_t lds = (size_t)9 * c * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
@@ -3471,6 +3610,33 @@ extern "C" int emsa_up2x_dw3x3_fwd_pair_t(int32_t dtype, const void* x0, const v
                                     (const emsa_f16*)skip0, (const emsa_f16*)skip1, (emsa_f16*)y0,
                                     (emsa_f16*)y1, n, h, w, c, st);
   return EMSA_E_SHAPE;
+}
+// emsa_up2x_dw3x3_fwd with the skip path's BatchNorm + ReLU formed at the skip load (SKBN above):
+// skip_y = the BatchNorm's input, scale / shift = its folded affine form (emsa_bn_finalize)
+extern "C" int emsa_up2x_dw3x3_fwd_skipbn(const float* x, const float* wdw, const float* bias,
+                                          const float* skip_y, const float* scale, const float* shift,
+                                          float* y, int32_t n, int32_t h, int32_t w, int32_t c,
+                                          void* stream) {
+  if (!x || !wdw || !y || !skip_y || !scale || !shift) return EMSA_E_ARG;
+  if (!c4_ok(c)) return EMSA_E_SHAPE;
+  const size_t lds = (size_t)11 * c * sizeof(float);
+  if (lds > 64 * 1024) return EMSA_E_SHAPE;
+  const long total = (long)n * 4 * h * w * (c / 4);
+  const dim3 grid(grid_for(total)), block(kThreads);
+  hipStream_t st = (hipStream_t)stream;
+  const bool nt = up2x_nt(c);
+#define EMSA_UP_SKBN(NTF, I)                                                                        \
+  hipLaunchKernelGGL((up2x_dw_fwd_kernel<float, float, NTF, I, true, true>), grid, block, lds, st, x, \
+                     wdw, bias, skip_y, y, n, h, w, c / 4, (const float*)nullptr,                   \
+                     (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,           \
+                     (float*)nullptr, scale, shift)
+  if (idx32_ok((long)n * 4 * h * w * c)) {
+    if (nt) EMSA_UP_SKBN(true, uint32_t); else EMSA_UP_SKBN(false, uint32_t);
+  } else {
+    if (nt) EMSA_UP_SKBN(true, long); else EMSA_UP_SKBN(false, long);
+  }
+#undef EMSA_UP_SKBN
+  return emsa_launch_status();
 }
 extern "C" int emsa_up2x_dw3x3_fwd(const float* x, const float* wdw, const float* bias, const float* skip, float* y, int32_t n, int32_t h, int32_t w, int32_t c, void* stream) {
   return up2x_dw3x3_fwd_impl<float, float>(x, wdw, bias, skip, y, n, h, w, c, stream);

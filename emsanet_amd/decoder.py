@@ -19,7 +19,7 @@ import torch.nn as nn
 from . import functional as Fn
 from . import ops
 from .nn import (BasicBlock, ConvNormAct, LearnedUpsampling, NonBottleneck1D, Spec, make_plain_conv_rt, make_upsampling,
-                 plain_conv)
+                 plain_conv, _fast_eval)
 from .postprocessing import (InstancePostprocessing, PanopticPostprocessing, gt_instance_orientations,
                              softmax_argmax)
 
@@ -98,8 +98,21 @@ class DecoderModule(nn.Module):
         x = self.blocks(self.conv3x3(x))
         side = side_head(x) if self.training else None
         if self.skip_fusion is not None:
+            if self._folds_skip(x):
+                # the skip path's BatchNorm + ReLU happens where the up-sampler loads its skip value
+                sf, up = self.skip_fusion, self.upsampling
+                return ops.SkipUpsampleFunction.apply(
+                    x, skip, sf._crt, sf._brt, up.conv.weight, up.conv.bias, sf.conv.weight,
+                    sf.norm.weight, sf.norm.bias), side
             skip = self.skip_fusion(skip)
         return self.upsampling(x, skip), side
+
+    def _folds_skip(self, x):
+        sf, up = self.skip_fusion, self.upsampling
+        if _fast_eval(sf) or not sf._brt.batch_stats():
+            return False                  # eval mode and frozen statistics keep their own paths
+        covered = isinstance(up, LearnedUpsampling) and up.c_pad == up.c and sf.act == ops.ACT_RELU
+        return Fn.skip_fold(x, sf.conv.in_channels, sf.conv.out_channels, covered)
 
 
 class DecoderBody(nn.Module):

@@ -735,10 +735,14 @@ def _conv_dgrad_phased(dy, wpd, spec, in_hw, mask_src, residual, out):
 
 
 def conv_dgrad(dy, wpd, spec, in_hw, mask_src=None, residual=None, out=None, wino_u=None,
-               mask_bits=None, wfrag=None, wino2d_u=None):
+               mask_bits=None, wfrag=None, wino2d_u=None, res_bits=None):
     """dx = conv_transpose(dy); optional fused `* (mask_src > 0)` -- or the same mask as bits
     (`mask_bits`, Winograd kernel only) -- and `+ residual`.  wino2d_u = the F(2x2,3x3)
-    data-gradient weights of a dense 3x3 conv; falls back to `wino_u` as conv_fwd does."""
+    data-gradient weights of a dense 3x3 conv; falls back to `wino_u` as conv_fwd does.
+    res_bits (1-D Winograd kernel only, `dgrad_takes_res_bits`): the residual arrives unmasked, its
+    ReLU mask beside it as bits in that kernel's layout -- `+ (bit ? residual : 0)`"""
+    if res_bits is not None:
+        return _conv_dgrad_resmask(dy, spec, in_hw, residual, res_bits, _resolve(wino_u), out)
     n = dy.shape[0]
     h, w = in_hw
     code = dt(dy)
@@ -788,6 +792,54 @@ def conv_dgrad(dy, wpd, spec, in_hw, mask_src=None, residual=None, out=None, win
         check(call_t('emsa_conv_igemm', code, g, _p(dy), _p(wpd), _p(out), None, None, None, None,
                      _p(residual), lr, _p(mask_src), lm, ACT_NONE, _stream()),
               'emsa_conv_igemm(dgrad)')
+    return out
+
+
+# The NBt1D block's masked skip gradient dres = dout * (out > 0) is read once -- as the residual of
+# conv3x1_1's data gradient, or as the gradient entering bnds' backward in a down-sampling block.  With
+# bn2's ReLU bit mask written in the Winograd epilogue's layout (bn_act wino_bits) that reader forms it
+# from dout and 1/32 of its bytes in mask bits: bn2's backward apply pass stores one tensor less and
+# dres is never allocated.  fp32, batch statistics, c % 64 == 0; where conv3x1_1's data gradient
+# does not run on the 1-D Winograd kernel dres is stored as before (DRES_FALLBACKS counts those:
+# 0 in the model).  EMSA_DRES_FOLD=0 switches it off; tests: DRES_FOLD = True / False.
+_DRES_FOLD_ENV = os.environ.get('EMSA_DRES_FOLD')
+DRES_FOLD = None
+DRES_FALLBACKS = 0
+
+
+def dres_fold():
+    if DRES_FOLD is not None:
+        return bool(DRES_FOLD)
+    return _DRES_FOLD_ENV != '0'
+
+
+def _dres_fell_back():
+    global DRES_FALLBACKS
+    DRES_FALLBACKS += 1
+
+
+def dgrad_takes_res_bits(spec, dy, in_hw, residual):
+    """the data gradient of conv `spec` (cotangent dy) runs on the launch that masks its residual by
+    bits (host-side decision, no launch)"""
+    if dy.dtype != torch.float32 or residual.dtype != torch.float32 or not wino_eligible(spec) \
+            or wino_rows(spec) != 1:
+        return False
+    h, w = in_hw
+    g = spec.geom_dgrad(dy.shape[0], h, w, ld_of(dy), spec.cin)
+    return _lib.lib().emsa_conv1d_wino_resmask_supported(g, ld_of(residual)) == 1
+
+
+def _conv_dgrad_resmask(dy, spec, in_hw, residual, res_bits, wino_u, out=None):
+    n = dy.shape[0]
+    h, w = in_hw
+    assert wino_u is not None and residual is not None and getattr(res_bits, '_emsa_wbits', False)
+    assert tuple(residual.shape) == (n, spec.cin, h, w)
+    if out is None:
+        out = act_empty(n, spec.cin, h, w, dy.device)
+    g = spec.geom_dgrad(n, h, w, ld_of(dy), ld_of(out))
+    check(_lib.lib().emsa_conv1d_wino_resmask(g, _p(dy), _p(wino_u), _p(out), _p(residual),
+                                              ld_of(residual), _p(res_bits), _stream()),
+          'emsa_conv1d_wino_resmask')
     return out
 
 
@@ -1227,9 +1279,40 @@ def bn_fold(gamma, beta, running_mean, running_var, eps, out=None):
     return buf[0], buf[1], buf[2]               # scale, shift, invstd
 
 
-def bn_act(x, scale, shift, drop=None, residual=None, act=ACT_NONE, want_mask=False):
+def wino_bits_ok(x):
+    """the ReLU bit mask of activation x can be written in the Winograd epilogue's layout"""
+    return x.dtype == torch.float32 and x.shape[1] % 64 == 0
+
+
+# The down-sampling shortcut idn = bnds(conv1x1(x)) of an NBt1D block is read once, as the residual
+# of bn2's normalise pass: with bn_act(res_affine=) that pass forms it from the conv output yd and
+# bnds' (scale, shift), and the shortcut's own normalise pass and tensor disappear (six blocks of the
+# model).  fp32, batch statistics.  Measured (profiles/dres_skip_*): the pass is gone from the
+# one-stream kernel table (bn_act_fwd_fast<float, false, false> 0.335 -> 0.230 ms per profiled step, 7
+# launches less; bn2's pass with the affine residual costs what it did: 1.823 -> 1.671 + 0.168 ms) but
+# the step does not tell it from its own spread (345.94 / 345.95 images/s with it against 344.70 /
+# 345.68 / 346.19 / 345.15 without): OFF by default, EMSA_IDN_FOLD=1 switches it on; tests: IDN_FOLD =
+# True / False.
+_IDN_FOLD_ENV = os.environ.get('EMSA_IDN_FOLD')
+IDN_FOLD = None
+
+
+def idn_fold(t):
+    if t.dtype != torch.float32:
+        return False
+    if IDN_FOLD is not None:
+        return bool(IDN_FOLD)
+    return _IDN_FOLD_ENV is not None and _IDN_FOLD_ENV != '0'
+
+
+def bn_act(x, scale, shift, drop=None, residual=None, act=ACT_NONE, want_mask=False, wino_bits=False,
+           res_affine=None):
     """y = act((x*scale + shift)*drop + residual); want_mask: also (y > 0) as a bit mask
-    (int64 words) that `bn_bwd` reads instead of y  -> y or (y, mask)"""
+    (int64 words) that `bn_bwd` reads instead of y  -> y or (y, mask).  wino_bits (fp32, c % 64 == 0,
+    ReLU): the mask in the layout the Winograd data gradient reads as `res_bits` (conv_dgrad): one word
+    per (pixel, 64-channel tile); the tensor carries `_emsa_wbits`, bn_bwd reads either layout.
+    res_affine = (scale, shift) (fp32): the residual added is residual * scale + shift, a BatchNorm
+    without activation applied to `residual` on the fly"""
     n, c, h, w = x.shape
     assert ld_of(x) == c and (residual is None or ld_of(residual) == c)
     y = act_empty(n, c, h, w, x.device, dtype=x.dtype)
@@ -1237,6 +1320,21 @@ def bn_act(x, scale, shift, drop=None, residual=None, act=ACT_NONE, want_mask=Fa
     bits = None
     if want_mask and act == ACT_RELU:
         bits = _empty((L.emsa_relu_mask_words(n * c * h * w),), x.device, torch.int64)
+    if res_affine is not None:
+        assert residual is not None and x.dtype == residual.dtype == torch.float32
+        assert not wino_bits or (bits is not None and wino_bits_ok(x))
+        check(L.emsa_bn_act_fwd_raff(_p(x), _p(y), _p(scale), _p(shift), _p(drop), _p(residual),
+                                     _p(res_affine[0]), _p(res_affine[1]), n, h * w, c, act, _p(bits),
+                                     1 if wino_bits else 0, _stream()), 'emsa_bn_act_fwd_raff')
+        if wino_bits:
+            bits._emsa_wbits = True
+        return (y, bits) if want_mask else y
+    if wino_bits:
+        assert bits is not None and wino_bits_ok(x)
+        check(L.emsa_bn_act_fwd_wbits(_p(x), _p(y), _p(scale), _p(shift), _p(drop), _p(residual), n,
+                                      h * w, c, act, _p(bits), _stream()), 'emsa_bn_act_fwd_wbits')
+        bits._emsa_wbits = True
+        return y, bits
     check(call_t('emsa_bn_act_fwd', dt(x), _p(x), _p(y), _p(scale), _p(shift), _p(drop),
                  _p(residual), n, h * w, c, act, _p(bits), _stream()), 'emsa_bn_act_fwd')
     return (y, bits) if want_mask else y
@@ -1255,13 +1353,25 @@ def bn_bwd(dy, y, x, gamma, mean, invstd, drop, act, train, want_dres, dg_out=No
         y, bits = None, y
     rows = L.emsa_bn_bwd_rows(n * h * w, c)
     partial = _empty((2, rows, c), x.device)
-    check(call_t('emsa_bn_bwd_reduce', code, _p(dy), _p(y), _p(bits), _p(x), _p(mean), _p(invstd),
-                 _p(drop), n, h * w, c, act, _p(partial), _stream()), 'emsa_bn_bwd_reduce')
+    wbits = bits is not None and getattr(bits, '_emsa_wbits', False)
+    if wbits:
+        assert act == ACT_RELU and code == 0
+        check(L.emsa_bn_bwd_reduce_wbits(_p(dy), _p(bits), _p(x), _p(mean), _p(invstd), _p(drop), n,
+                                         h * w, c, _p(partial), _stream()), 'emsa_bn_bwd_reduce_wbits')
+    else:
+        check(call_t('emsa_bn_bwd_reduce', code, _p(dy), _p(y), _p(bits), _p(x), _p(mean), _p(invstd),
+                     _p(drop), n, h * w, c, act, _p(partial), _stream()), 'emsa_bn_bwd_reduce')
     dx = act_empty(n, c, h, w, x.device, dtype=x.dtype)
     dres = act_empty(n, c, h, w, x.device, dtype=x.dtype) if want_dres else None
     if dg_out is None or db_out is None:
         dgb = _empty((2, c), x.device)
         dg_out, db_out = dgb[0], dgb[1]
+    if wbits:
+        check(L.emsa_bn_bwd_apply_wbits(_p(dy), _p(bits), _p(x), _p(gamma), _p(mean), _p(invstd),
+                                        _p(drop), _p(partial), rows, n, h * w, c, 1 if train else 0,
+                                        _p(dx), _p(dres), _p(dg_out), _p(db_out), _stream()),
+              'emsa_bn_bwd_apply_wbits')
+        return dx, dres, dg_out, db_out
     check(call_t('emsa_bn_bwd_apply', code, _p(dy), _p(y), _p(bits), _p(x), _p(gamma), _p(mean),
                  _p(invstd), _p(drop), _p(partial), rows, n, h * w, c, act, 1 if train else 0,
                  _p(dx), _p(dres), _p(dg_out), _p(db_out), _stream()), 'emsa_bn_bwd_apply')
@@ -1550,6 +1660,60 @@ def up2x_dw_fwd(x, wdw, bias, skip=None, out_f32=False):
                   dtype=torch.float32 if out_f32 else x.dtype)
     check(_two('emsa_up2x_dw3x3_fwd', x, out_f32, _p(x), _p(wdw), _p(bias), _p(skip), _p(y), n, h,
                w, c, _stream()), 'emsa_up2x_dw3x3_fwd')
+    return y
+
+
+# The decoder's skip path, 1x1 conv -> BatchNorm -> ReLU, is read by nothing but the learned
+# up-sampling's skip add: with relu(y * scale + shift) formed where the up-sampler loads its skip value
+# (emsa_up2x_dw3x3_fwd_skipbn) the activation a and its ReLU bit mask are never stored, and the
+# BatchNorm's backward passes recompute the decisions from y (bn_bwd_aff).  What leaves the step is
+# the normalise pass over the skip tensor (read y, write a: 79 / 157 / 314 MB at /16 /8 /4 per
+# decoder at the benchmark size).  fp32, batch statistics.  Default: fold when the skip tensor is at
+# least EMSA_SKIP_FOLD_MIN_MB (24) MiB, the floor of the bn1 fold; EMSA_SKIP_FOLD=0 / 1 forces never /
+# always.  tests: SKIP_FOLD = True / False.
+_SKIP_FOLD_ENV = os.environ.get('EMSA_SKIP_FOLD')
+_SKIP_FOLD_MIN_BYTES = int(float(os.environ.get('EMSA_SKIP_FOLD_MIN_MB', '24')) * (1 << 20))
+SKIP_FOLD = None
+
+# forward passes that were asked to fold (switch forced on) in a configuration the fold does not
+# cover and ran today's kernels instead: 0 for the model bench.py trains
+SKIP_FOLD_FALLBACKS = 0
+
+
+def skip_fold_forced():
+    """True / False when the switch is forced, None when the size rule decides"""
+    if SKIP_FOLD is not None:
+        return bool(SKIP_FOLD)
+    if _SKIP_FOLD_ENV is not None:
+        return _SKIP_FOLD_ENV != '0'
+    return None
+
+
+def skip_fold(x, skip_c, c, covered):
+    """fold the skip path's BatchNorm + ReLU into the up-sampler that maps x (n, c, h, w) to twice
+    its size?  `covered`: the caller's configuration is one the fold is built for"""
+    global SKIP_FOLD_FALLBACKS
+    forced = skip_fold_forced()
+    if forced is False:
+        return False
+    n, _, h, w = x.shape
+    ok = covered and x.dtype == torch.float32 and x.shape[1] == c and c % 4 == 0 and 11 * c * 4 <= 65536
+    if forced:
+        if not ok:
+            SKIP_FOLD_FALLBACKS += 1
+        return ok
+    return ok and n * c * 4 * h * w * 4 >= _SKIP_FOLD_MIN_BYTES
+
+
+def up2x_dw_fwd_skipbn(x, wdw, bias, skip_y, scale, shift):
+    """up2x_dw_fwd(x, wdw, bias, relu(skip_y * scale + shift)) without the activation in memory"""
+    n, c, h, w = x.shape
+    assert x.dtype == skip_y.dtype == torch.float32 and ld_of(x) == c and ld_of(skip_y) == c
+    assert tuple(skip_y.shape) == (n, c, 2 * h, 2 * w)
+    y = act_empty(n, c, 2 * h, 2 * w, x.device)
+    check(_lib.lib().emsa_up2x_dw3x3_fwd_skipbn(_p(x), _p(wdw), _p(bias), _p(skip_y), _p(scale),
+                                                _p(shift), _p(y), n, h, w, c, _stream()),
+          'emsa_up2x_dw3x3_fwd_skipbn')
     return y
 
 

@@ -157,6 +157,11 @@ class ConvRT:
                                  mask_bits=mask_bits, **kw)
         return Fn.conv_dgrad(dy, self.packed_dgrad(), self.spec, in_hw, **kw)
 
+    def dgrad_takes_res_bits(self, dy, in_hw, residual):
+        """this conv's data gradient can mask its residual operand by bits (Fn.conv_dgrad res_bits):
+        the fp32 1-D Winograd launch, whole 64-channel tiles"""
+        return self.wino and not self.wino2d and Fn.dgrad_takes_res_bits(self.spec, dy, in_hw, residual)
+
     def _row_dgrad_weights(self):
         ud = self._wino_weights()[1]
         if ud is None:
@@ -613,10 +618,11 @@ class BNRT:
         return s, t
 
 
-def _conv_bn_forward(x, crt, brt, act, drop=None, residual=None):
+def _conv_bn_forward(x, crt, brt, act, drop=None, residual=None, wino_bits=False, res_affine=None):
     """conv (+bias) -> BN (batch or frozen statistics) -> *drop -> +residual -> act.
     returns out, y_raw, mean, invstd, relu_mask (bit mask of out > 0 for the backward pass, or
-    None without ReLU)"""
+    None without ReLU; wino_bits: in the Winograd epilogue's layout, Fn.bn_act).  res_affine: the
+    residual is `residual * scale + shift` (Fn.bn_act)"""
     bias = crt.conv.bias.detach() if crt.conv.bias is not None else None
     if brt.batch_stats():
         y, stats = crt.forward(x, bias=bias, want_stats=True)
@@ -624,7 +630,8 @@ def _conv_bn_forward(x, crt, brt, act, drop=None, residual=None):
     else:
         y, stats, count = crt.forward(x, bias=bias), None, 0
     scale, shift, mean, invstd = brt.forward_stats(stats, count)
-    out, mask = Fn.bn_act(y, scale, shift, drop, residual, act, want_mask=True)
+    out, mask = Fn.bn_act(y, scale, shift, drop, residual, act, want_mask=True, wino_bits=wino_bits,
+                          res_affine=res_affine)
     # (the affine form travels with the statistics: a data gradient with the fused BatchNorm
     #  reduction recomputes the ReLU mask from it)
     if brt.batch_stats():                # (`mean` is this call's own tensor, not the running buffer)
@@ -767,12 +774,13 @@ def _flush_wgrads(defer, grads):
 
 
 def _conv_backward(x, dy, crt, need_dx, mask_src=None, residual=None, mask_bits=None, bnb=None,
-                   in_affine=None, defer=None):
+                   in_affine=None, defer=None, res_bits=None):
     """-> dx (or None), dw (OIHW), dbias (or None); with bnb = (t, (scale, shift), mean, invstd) of
     the BatchNorm+ReLU in front of the conv: -> dx, dw, dbias, (partial, rows) or None -- dx then
     already carries that ReLU's mask (ConvRT.dgrad_bnb).  in_affine: the forward folded that
     BatchNorm + ReLU into the conv's loader (x = the BatchNorm's INPUT).  defer: a list -- the
-    weight gradient is not launched here but queued (`_flush_wgrads`), dw / dbias are placeholders"""
+    weight gradient is not launched here but queued (`_flush_wgrads`), dw / dbias are placeholders.
+    res_bits: `residual` is unmasked, its ReLU mask travels as bits (ConvRT.dgrad_takes_res_bits)"""
     conv = crt.conv
     _trace_grad(conv, dy)
     # the gradients go straight into their flat all-reduce / optimizer bucket views when
@@ -800,7 +808,9 @@ def _conv_backward(x, dy, crt, need_dx, mask_src=None, residual=None, mask_bits=
         if in_affine is not None:
             raise _lib.EmsaError("folded BatchNorm: the data gradient has no fused reduction here")
         return crt.dgrad(dy, x.shape[2:], residual=residual), dw, db, None
-    if need_dx:
+    if need_dx and res_bits is not None:
+        dx = crt.dgrad(dy, x.shape[2:], residual=residual, res_bits=res_bits)
+    elif need_dx:
         dx = crt.dgrad(dy, x.shape[2:], mask_src=mask_src, residual=residual,
                        mask_bits=mask_bits)
     return dx, dw, db
@@ -857,12 +867,27 @@ class NBt1DFunction(Function):
         else:
             a2, y2, m1, is1, k1 = _conv_bn_forward(y1, rt.c13_1, rt.bn1, ACT_RELU)
             y3, q3 = rt.c31_2.forward(a2, bias=b(rt.c31_2), act=ACT_RELU, want_relu_bits=True)
-        if rt.cds is not None:
+        aff_d = None
+        if rt.cds is not None and rt.bnds.batch_stats() and rt.bn2.batch_stats() and Fn.idn_fold(y3):
+            # the shortcut's normalise happens inside bn2's pass (Fn.idn_fold): idn is never written
+            yd, stats = rt.cds.forward(x, want_stats=True)
+            sd, td, md, isd = rt.bnds.forward_stats(stats, yd.shape[0] * yd.shape[2] * yd.shape[3])
+            md._emsa_affine = aff_d = (sd, td)
+            idn = yd
+        elif rt.cds is not None:
             idn, yd, md, isd, _ = _conv_bn_forward(x, rt.cds, rt.bnds, ACT_NONE)
         else:
             idn, yd, md, isd = x, None, None, None
+        # k2 in the layout conv3x1_1's data gradient (bnds' backward in a down-sampling block) reads:
+        # the masked skip gradient dres is then formed where it is consumed (Fn.dres_fold)
+        wbits = False
+        if y3.dtype == torch.float32 and rt.bn2.batch_stats() and Fn.dres_fold():
+            wbits = Fn.wino_bits_ok(y3) and y3.shape[1] == rt.c13_2.spec.cout and \
+                (rt.cds is not None or (rt.c31_1.wino and not rt.c31_1.wino2d))
+            if not wbits:
+                Fn._dres_fell_back()
         out, y4, m2, is2, k2 = _conv_bn_forward(y3, rt.c13_2, rt.bn2, ACT_RELU, drop=drop,
-                                                residual=idn)
+                                                residual=idn, wino_bits=wbits, res_affine=aff_d)
         if MASK_TRACE is not None:
             a2t = a2 if a2 is not None else Fn.bn_act(y2, scale, shift, None, None, ACT_RELU)
             for tag, t in (('nbt.y1', y1), ('nbt.a2', a2t), ('nbt.y3', y3), ('nbt.out', out)):
@@ -890,8 +915,14 @@ class NBt1DFunction(Function):
         defer = []           # the block's weight gradients: launched together at the end
 
         # out = relu(bn2(y4)*drop + idn)
+        # (k2 in the Winograd layout: dres = dout * k2 is not stored, its one reader forms it)
+        fold = getattr(k2, '_emsa_wbits', False)
+        if fold and rt.cds is None and need_dx and \
+                not rt.c31_1.dgrad_takes_res_bits(y1, x.shape[2:], dout):
+            fold = False
+            Fn._dres_fell_back()
         dy4, dres, dg2, db2 = Fn.bn_bwd(dout, k2, y4, rt.bn2.bn.weight.detach(), m2, is2, drop,
-                                        ACT_RELU, t2, want_dres=True, **_bn_targets(rt.bn2))
+                                        ACT_RELU, t2, want_dres=not fold, **_bn_targets(rt.bn2))
         # conv1x3_2 (input y3 = relu(.)): ReLU mask fused into the dgrad epilogue
         dz3, dw4, dbias4 = _conv_backward(y3, dy4, rt.c13_2, True, mask_src=y3, mask_bits=q3,
                                           defer=defer)
@@ -921,11 +952,20 @@ class NBt1DFunction(Function):
         grads = []
         if rt.cds is None:
             # identity skip: dx = dgrad(conv3x1_1) + dres, add fused into the epilogue
-            dx, dw1, dbias1 = _conv_backward(x, dz1, rt.c31_1, need_dx, residual=dres, defer=defer)
+            if fold:
+                dx, dw1, dbias1 = _conv_backward(x, dz1, rt.c31_1, need_dx, residual=dout,
+                                                 res_bits=k2, defer=defer)
+            else:
+                dx, dw1, dbias1 = _conv_backward(x, dz1, rt.c31_1, need_dx, residual=dres, defer=defer)
         else:
-            dyd, _, dgd, dbd = Fn.bn_bwd(dres, None, yd, rt.bnds.bn.weight.detach(), md, isd,
-                                         None, ACT_NONE, tds, want_dres=False,
-                                         **_bn_targets(rt.bnds))
+            if fold:           # the masked incoming gradient: dout with k2 as its ReLU mask
+                dyd, _, dgd, dbd = Fn.bn_bwd(dout, k2, yd, rt.bnds.bn.weight.detach(), md, isd,
+                                             None, ACT_RELU, tds, want_dres=False,
+                                             **_bn_targets(rt.bnds))
+            else:
+                dyd, _, dgd, dbd = Fn.bn_bwd(dres, None, yd, rt.bnds.bn.weight.detach(), md, isd,
+                                             None, ACT_NONE, tds, want_dres=False,
+                                             **_bn_targets(rt.bnds))
             dxd, dwd, _ = _conv_backward(x, dyd, rt.cds, need_dx)
             dx, dw1, dbias1 = _conv_backward(x, dz1, rt.c31_1, need_dx, residual=dxd, defer=defer)
         grads = [dw1, dbias1, dw2, dbias2, dg1, db1, dw3, dbias3, dw4, dbias4, dg2, db2]
@@ -1591,6 +1631,47 @@ class UpsampleDWFunction(Function):
         if has_skip:
             dskip = dy if dy.dtype == x.dtype else Fn.cast(dy, x.dtype)
         return dx, dw.reshape(ctx.wshape), (db if has_bias else None), dskip, None
+
+
+class SkipUpsampleFunction(Function):
+    """up2x(x) + relu(bn(conv1x1(skip))) of a decoder module with the skip path's BatchNorm + ReLU
+    formed inside the up-sampler (Fn.skip_fold): what ConvBNActFunction followed by
+    UpsampleDWFunction computes, bit for bit, without the activation and its ReLU bit mask in memory.
+    Batch statistics, fp32.  Saved for the backward pass: x, skip, the conv output y and per-channel
+    vectors."""
+
+    @staticmethod
+    def forward(ctx, x, skip, crt, brt, wdw, bias, weight, gamma, beta):
+        x, skip = Fn.as_act(x, dense=True), Fn.as_act(skip)
+        cb = crt.conv.bias.detach() if crt.conv.bias is not None else None
+        y, stats = crt.forward(skip, bias=cb, want_stats=True)
+        scale, shift, mean, invstd = brt.forward_stats(stats, y.shape[0] * y.shape[2] * y.shape[3])
+        if MASK_TRACE is not None:            # (tests: the activation exists for the trace only)
+            _trace_mask('conv_bn_act', Fn.bn_act(y, scale, shift, None, None, ACT_RELU))
+        w = wdw.detach().contiguous()
+        out = Fn.up2x_dw_fwd_skipbn(x, w, bias.detach() if bias is not None else None, y, scale, shift)
+        ctx.crt, ctx.brt = crt, brt
+        ctx.save_for_backward(x, w, skip)
+        ctx.saved = (y, scale, shift, mean, invstd)
+        ctx.has_bias, ctx.wshape = bias is not None, wdw.shape
+        return out
+
+    @staticmethod
+    @once_differentiable
+    @_traced
+    def backward(ctx, dy):
+        x, w, skip = ctx.saved_tensors
+        y, scale, shift, mean, invstd = ctx.saved
+        ctx.saved = None
+        dy = Fn.as_act(dy, dense=True)
+        dx, dw, db = Fn.up2x_dw_bwd(dy, x, w, need_dx=ctx.needs_input_grad[0])
+        # the up-sampler's cotangent is the skip activation's: bn backward with the ReLU decisions
+        # recomputed from y, then the 1x1 conv's gradients
+        dyk, dg, dbeta = Fn.bn_bwd_aff(dy, y, ctx.brt.bn.weight.detach(), mean, invstd,
+                                       (scale, shift), **_bn_targets(ctx.brt))
+        dskip, dwc, _ = _conv_backward(skip, dyk, ctx.crt, ctx.needs_input_grad[1])
+        return (dx, dskip, None, None, dw.reshape(ctx.wshape), db if ctx.has_bias else None, dwc,
+                dg, dbeta)
 
 
 class PlainUpsampleFunction(Function):

@@ -159,6 +159,17 @@ int emsa_conv1d_wino_bnb(const EmsaConvGeom* g, const float* dy, const float* u,
                          const float* residual, int32_t ld_res, const float* t, int32_t ld_t,
                          const float* bn_scale, const float* bn_shift, const float* bn_mean,
                          const float* bn_invstd, float* partial, int32_t rows_alloc, void* stream);
+/* Data gradient whose residual operand arrives UNMASKED with its ReLU mask beside it as bits:
+ *   out = conv_transpose(dy) + (bit ? residual : 0)
+ * res_bits: one 64-bit word per (pixel, 64-channel tile of `out`), bit comp * 16 + col4 -- the layout
+ * of emsa_conv1d_wino's relu_bits, written for a BatchNorm output by emsa_bn_act_fwd_wbits.  The
+ * masked residual (an NBt1D block's skip gradient dout * (out > 0)) is never stored.
+ * emsa_conv1d_wino_resmask_supported: 1 where the launch takes (g, ld_res) -- a geometry of
+ * emsa_conv1d_wino_supported with n_ch % 64 == 0 --, decided on the host without a launch.        */
+int emsa_conv1d_wino_resmask_supported(const EmsaConvGeom* g, int32_t ld_res);
+int emsa_conv1d_wino_resmask(const EmsaConvGeom* g, const float* dy, const float* u, float* out,
+                             const float* residual, int32_t ld_res, const uint64_t* res_bits,
+                             void* stream);
 /* The NBt1D block's bn1 folded into its consumers (/root/reference/emsanet/model.py:47-58: conv1x3_1
  * -> BatchNorm -> ReLU -> conv3x1_2): the forward conv and its weight gradient read the BatchNorm's
  * INPUT `in` and form a = relu(in * in_scale[c] + in_shift[c]) (c = input channel, k_ch floats each;
@@ -307,6 +318,29 @@ int emsa_bn_bwd_apply(const float* dy, const float* y, const uint64_t* mask_bits
                       float* partial, int32_t rows, int32_t n_img, int64_t hw, int32_t c,
                       int32_t act, int32_t train, float* dx, float* dres, float* dgamma,
                       float* dbeta, void* stream);
+/* The three passes with the ReLU bit mask in the layout the Winograd epilogue reads
+ * (emsa_conv1d_wino_resmask): one word per (pixel, 64-channel tile), bit comp * 16 + col4 with channel
+ * = tile * 64 + col4 * 4 + comp.  fp32, c % 64 == 0, act = ReLU; emsa_relu_mask_words words as
+ * before.  Values, partial rows and sums are those of the three functions above, bit for bit.     */
+int emsa_bn_act_fwd_wbits(const float* x, float* y, const float* scale, const float* shift,
+                          const float* drop, const float* residual, int32_t n_img, int64_t hw,
+                          int32_t c, int32_t act, uint64_t* mask_bits, void* stream);
+/* emsa_bn_act_fwd whose residual operand is the INPUT of another BatchNorm without activation (the
+ * down-sampling shortcut of an NBt1D block): y = act((x*scale + shift)*drop + (res_src*res_scale +
+ * res_shift)); bit-identical to emsa_bn_act_fwd(res_src -> idn) followed by emsa_bn_act_fwd(x, idn).
+ * wbits != 0: mask_bits in the layout of emsa_bn_act_fwd_wbits.  fp32.                            */
+int emsa_bn_act_fwd_raff(const float* x, float* y, const float* scale, const float* shift,
+                         const float* drop, const float* res_src, const float* res_scale,
+                         const float* res_shift, int32_t n_img, int64_t hw, int32_t c, int32_t act,
+                         uint64_t* mask_bits, int32_t wbits, void* stream);
+int emsa_bn_bwd_reduce_wbits(const float* dy, const uint64_t* mask_bits, const float* x,
+                             const float* save_mean, const float* save_invstd, const float* drop,
+                             int32_t n_img, int64_t hw, int32_t c, float* partial, void* stream);
+int emsa_bn_bwd_apply_wbits(const float* dy, const uint64_t* mask_bits, const float* x,
+                            const float* gamma, const float* save_mean, const float* save_invstd,
+                            const float* drop, float* partial, int32_t rows, int32_t n_img,
+                            int64_t hw, int32_t c, int32_t train, float* dx, float* dres,
+                            float* dgamma, float* dbeta, void* stream);
 /* one Dropout2d layer of emsa_dropout2d_mask_batch: masks of layer `layer_id` (probability p, c
  * channels) go to masks[offset ...]                                                               */
 typedef struct EmsaDropoutJob {
@@ -371,6 +405,13 @@ int emsa_se_scale_bwd_apply(const float* dout, const float* s, const float* dgap
  *   x [n][h][w][c] -> y [n][2h][2w][c];  wdw [c][3][3] (OIHW of a depth-wise conv), bias [c]  */
 int emsa_up2x_dw3x3_fwd(const float* x, const float* wdw, const float* bias, const float* skip,
                         float* y, int32_t n, int32_t h, int32_t w, int32_t c, void* stream);
+/* The same with the skip path's BatchNorm + ReLU formed where the skip value is loaded: skip_y
+ * [n][2h][2w][c] is the BatchNorm's INPUT, scale / shift [c] its folded affine form; the value added
+ * is relu(skip_y * scale + shift) with the fma and the maximum of emsa_bn_act_fwd, so y is
+ * bit-identical to emsa_bn_act_fwd followed by emsa_up2x_dw3x3_fwd.  fp32 only. */
+int emsa_up2x_dw3x3_fwd_skipbn(const float* x, const float* wdw, const float* bias,
+                               const float* skip_y, const float* scale, const float* shift, float* y,
+                               int32_t n, int32_t h, int32_t w, int32_t c, void* stream);
 int emsa_up2x_dw3x3_bwd_data(const float* dy, const float* wdw, float* dx, int32_t n, int32_t h,
                              int32_t w, int32_t c, void* stream);
 /* dw [c][9] and db [c] accumulated with atomics: zero them first */
