@@ -295,6 +295,12 @@ SIGNATURES = {
     'emsa_dropout2d_mask_dev': (c_int, [_P, c_int32, c_int32, c_float, _P, c_uint32, _P]),
     'emsa_u32_add': (c_int, [_P, c_uint32, _P]),
     'emsa_sgd_nesterov_dev': (c_int, [_P, _P, _P, c_int64, _P, _P]),
+    'emsa_nonfinite_scan': (c_int, [_P, c_int64, _P, _P]),
+    'emsa_loss_scale_update': (c_int, [_P, c_float, c_float, c_int32, _P]),
+    'emsa_sgd_nesterov_ls': (c_int, [_P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_int32,
+                                     _P, _P, _P]),
+    'emsa_adam_advance_ls': (c_int, [_P, _P, _P, _P]),
+    'emsa_adam_step_ls': (c_int, [_P, _P, _P, _P, c_int64, _P, _P, _P, _P]),
     'emsa_prof_enable': (c_int, [c_int32]),
     'emsa_prof_next_flops': (c_int, [ctypes.c_double]),
     'emsa_prof_reset': (c_int, []),

@@ -2503,13 +2503,14 @@ bool wgrad16_tr() {
 }
 // geometry admits the direct 16-bit kernel (8-byte accesses: 4 channels; dout_is_aligned checks dy)
 bool direct16_geom(const EmsaConvGeom* g) { return wgrad16_direct() && !(g->k_ch & 3); }
-int64_t wgrad_ws_bytes(const EmsaConvGeom* g, size_t esize) {
+// wino16: the storage type has the opt-in Winograd form (bf16; see conv_wgrad_impl)
+int64_t wgrad_ws_bytes(const EmsaConvGeom* g, size_t esize, bool wino16 = true) {
   if (!geom_ok(g)) return 0;
   Wgrad1dPlan pl;
   const bool half = esize != sizeof(float);
   const bool d16 = half && direct16_geom(g);
   if (!plan_wgrad1d(g, dout_is_aligned(g, nullptr), pl, esize, d16)) return 0;
-  if (half && !d16 && !pl.wino) return 0;
+  if (half && !d16 && !(pl.wino && wino16)) return 0;
   return (int64_t)pl.ksplit * ((int64_t)pl.w.n_tiles * pl.w.R * pl.w.taps * 4096 +
                                (int64_t)pl.w.n_co_tiles * 64) * (int64_t)sizeof(float);
 }
@@ -2524,7 +2525,7 @@ extern "C" int64_t emsa_conv_wgrad_ws_bytes(const EmsaConvGeom* g) {
 }
 // workspace of emsa_conv_wgrad_t for activations of `dtype` (the split-K plan depends on it)
 extern "C" int64_t emsa_conv_wgrad_ws_bytes_t(int32_t dtype, const EmsaConvGeom* g) {
-  return wgrad_ws_bytes(g, dtype == EMSA_DT_F32 ? sizeof(float) : 2);
+  return wgrad_ws_bytes(g, dtype == EMSA_DT_F32 ? sizeof(float) : 2, dtype != EMSA_DT_F16);
 }
 
 namespace {
@@ -2533,11 +2534,15 @@ int conv_wgrad_impl(const EmsaConvGeom* g, const T* in_t, const T* dout_t, float
                     float* ws, void* stream, const float* in_scale = nullptr,
                     const float* in_shift = nullptr) {
   constexpr bool kHalf = sizeof(T) != 4;
+  // EMSA_WGRAD16=wino rounds the Winograd-transformed operands to bf16: a bf16 form only.  fp16
+  // storage under that switch runs the tap-group kernel (fp32 MFMA on the converted values).
+  constexpr bool kF16 = std::is_same<T, emsa_f16>::value;
   // (the argument structs carry byte addresses; the kernels read them through typed loaders)
   const float* in = reinterpret_cast<const float*>(in_t);
   const float* dout = reinterpret_cast<const float*>(dout_t);
   if (!geom_ok(g) || geom_mapped(g)) return EMSA_E_SHAPE;
   if (!in || !dout || !dw) return EMSA_E_ARG;
+  if (kF16 && in_scale) return EMSA_E_ARG;          // the loader fold is a bf16 / fp32 form
   if (g->div_h != 1 || g->div_w != 1) return EMSA_E_SHAPE;
   WgradArgs a;
   a.g = *g;
@@ -2555,7 +2560,7 @@ int conv_wgrad_impl(const EmsaConvGeom* g, const T* in_t, const T* dout_t, float
   const bool direct16 = kHalf && direct16_geom(g);
   if (direct16 && ((((uintptr_t)in) | ((uintptr_t)dout)) & 7)) return EMSA_E_SHAPE;
   const bool one_d = plan_wgrad1d(g, a.dout_aligned != 0, pl, sizeof(T), direct16) &&
-                     (!kHalf || direct16 || pl.wino);
+                     (!kHalf || direct16 || (pl.wino && !kF16));
   if (ws != nullptr && !one_d) return EMSA_E_SHAPE;   // ws_bytes(g) was 0
   if (one_d) {
     Wgrad1dArgs& w = pl.w;
@@ -2595,10 +2600,12 @@ int conv_wgrad_impl(const EmsaConvGeom* g, const T* in_t, const T* dout_t, float
                  !((((uintptr_t)in) | ((uintptr_t)dout)) & 15))
         {
           // (16-byte chunks: every pixel row of both tensors starts on a 16-byte boundary)
-          if (in_scale)
-            hipLaunchKernelGGL((conv_wgrad1d_tr_kernel<T, true>), grid, dim3(256),
-                               (size_t)2 * kWT_IMG * sizeof(T) + 2 * 64 * sizeof(float), st, w);
-          else
+          if (in_scale) {
+            // (no entry point hands fp16 a loader fold: that form is not instantiated)
+            if constexpr (!kF16)
+              hipLaunchKernelGGL((conv_wgrad1d_tr_kernel<T, true>), grid, dim3(256),
+                                 (size_t)2 * kWT_IMG * sizeof(T) + 2 * 64 * sizeof(float), st, w);
+          } else
             hipLaunchKernelGGL((conv_wgrad1d_tr_kernel<T>), grid, dim3(256),
                                (size_t)2 * kWT_IMG * sizeof(T), st, w);
         } else if (in_scale) {
@@ -2607,7 +2614,7 @@ int conv_wgrad_impl(const EmsaConvGeom* g, const T* in_t, const T* dout_t, float
         } else
           hipLaunchKernelGGL((conv_wgrad1d_h_kernel<T, 0>), grid, dim3(256),
                              (size_t)2 * 64 * kWH_ROW * sizeof(T), st, w);
-      } else
+      } else if constexpr (!kF16)
       // EMSA_WGRAD16=wino: E / D are formed in fp32 and rounded to bf16 as they enter LDS, one
       // v_mfma_f32_32x32x16_bf16 per Winograd component and K step
       hipLaunchKernelGGL((conv_wgrad1d_wino_kernel<BCO, BCI, true, T>),
@@ -2675,8 +2682,11 @@ extern "C" int emsa_conv_wgrad_inbn(const EmsaConvGeom* g, const float* in, cons
   return conv_wgrad_impl<float>(g, in, dout, dw, dbias, ws, stream, in_scale, in_shift);
 }
 
-// weight (+bias) gradient from activations in storage type `dtype` (training: EMSA_DT_BF16); the
-// gradients are fp32 (master weights), the workspace contract is that of emsa_conv_wgrad
+// weight (+bias) gradient from activations in storage type `dtype` (training: EMSA_DT_BF16, or
+// EMSA_DT_F16 under a loss scale); the gradients are fp32 (master weights), the workspace contract
+// is that of emsa_conv_wgrad.  The 16-bit kernels are one template over the element type: the
+// transposing LDS read is type-agnostic, only the MFMA (v_mfma_f32_32x32x16_bf16 / _f16) differs.
+// The multi-job launch and the BatchNorm loader fold (emsa_conv_wgrad_multi_t, *_inbn_t) stay bf16.
 extern "C" int emsa_conv_wgrad_t(int32_t dtype, const EmsaConvGeom* g, const void* in,
                                  const void* dout, float* dw, float* dbias, float* ws,
                                  void* stream) {
@@ -2685,6 +2695,9 @@ extern "C" int emsa_conv_wgrad_t(int32_t dtype, const EmsaConvGeom* g, const voi
   if (dtype == EMSA_DT_BF16)
     return conv_wgrad_impl<emsa_bf16>(g, (const emsa_bf16*)in, (const emsa_bf16*)dout, dw, dbias,
                                       ws, stream);
+  if (dtype == EMSA_DT_F16)
+    return conv_wgrad_impl<emsa_f16>(g, (const emsa_f16*)in, (const emsa_f16*)dout, dw, dbias,
+                                     ws, stream);
   return EMSA_E_ARG;
 }
 

@@ -136,10 +136,13 @@ class GraphedInference:
 class _TrainStateSnapshot:
     """everything a training step changes besides gradients: parameters + momentum (the flat
     buffers of FusedSGD), BatchNorm running statistics and step counters, Dropout2d step,
-    first-step flag"""
+    first-step flag, and the device state of a loss scaler (so that a warm-up neither moves the scale
+    nor counts its steps)"""
 
-    def __init__(self, model, optimizer, bns):
+    def __init__(self, model, optimizer, bns, loss_scaler=None):
         self.model, self.opt, self.bns = model, optimizer, bns
+        self.scaler = loss_scaler
+        self.scaler_state = loss_scaler.device_state.clone() if loss_scaler is not None else None
         self.params = [p.clone() for p in optimizer.flat_params]
         self.momentum = [m.clone() for m in optimizer.flat_momentum]
         self.buffers = [(b, b.clone()) for b in model.buffers()]
@@ -159,6 +162,8 @@ class _TrainStateSnapshot:
             b.copy_(src)
         for m, n in zip(self.bns, self.pending):
             m._emsa_pending = n
+        if self.scaler is not None:
+            self.scaler.device_state.copy_(self.scaler_state)
         self.opt._first = self.first
         self.opt._upload_hyper()
         self.model.dropout_step = self.dropout_step
@@ -187,8 +192,14 @@ class GraphedTrainStep:
     collectives issued from autograd hooks inside a capture are not supported here)."""
 
     def __init__(self, model, example_batch, buckets, optimizer, loss_fn=None, cotangents=None,
-                 warmup=3, keep_warmup_updates=False):
-        """The constructor has to RUN `warmup` real steps on `example_batch` before it can record one
+                 warmup=3, keep_warmup_updates=False, loss_scaler=None):
+        """loss_scaler (optim.LossScaler over `optimizer`; None: exactly the step described above):
+        the backward pass is seeded with the scaler's device scale and `scaler.step()` -- non-finite
+        scan, state update, scaled update, all captured -- takes the place of `optimizer.step()`.
+        Whether a replay updates the parameters is decided on the device; `replay()` needs nothing
+        new on the host.
+
+        The constructor has to RUN `warmup` real steps on `example_batch` before it can record one
         (they pack the weights, set kernel attributes and size the graph's memory pool).  By default
         their effects are taken back: parameters, momentum buffers, BatchNorm running statistics and
         step counters, the Dropout2d step and the optimizer's first-step flag are snapshotted before
@@ -202,7 +213,10 @@ class GraphedTrainStep:
                                       "see SegmentedGraphedTrainStep")
         if (loss_fn is None) == (cotangents is None):
             raise ValueError("give either loss_fn or cotangents")
+        if loss_scaler is not None and loss_scaler.opt is not optimizer:
+            raise ValueError("loss_scaler wraps another optimizer")
         self.model, self.buckets, self.opt = model, buckets, optimizer
+        self.scaler = loss_scaler
         self.loss_fn, self.cots = loss_fn, cotangents
         self.static_in = {k: v.clone() for k, v in example_batch.items() if torch.is_tensor(v)}
         self.extra = {k: v for k, v in example_batch.items() if not torch.is_tensor(v)}
@@ -210,7 +224,8 @@ class GraphedTrainStep:
         optimizer.use_device_hyperparameters(True)
         self._bns = [m for m in model.modules()
                      if hasattr(m, '_emsa_pending') and m.training]
-        snap = None if keep_warmup_updates else _TrainStateSnapshot(model, optimizer, self._bns)
+        snap = None if keep_warmup_updates else _TrainStateSnapshot(model, optimizer, self._bns,
+                                                                    loss_scaler)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -243,14 +258,22 @@ class GraphedTrainStep:
         self.buckets.reset()
         out = self.model({**self.static_in, **self.extra})
         flat = _flatten(out)
+        scaler = self.scaler
         if self.loss_fn is not None:
             loss = self.loss_fn(out)
-            loss.backward()
+            if scaler is not None:
+                scaler.backward(loss)
+            else:
+                loss.backward()
         else:
             loss = None
-            torch.autograd.backward(flat, self.cots)
+            torch.autograd.backward(flat, self.cots if scaler is None
+                                    else scaler.scale_cotangents(self.cots))
         self.buckets.finish()
-        self.opt.step()
+        if scaler is not None:
+            scaler.step()
+        else:
+            self.opt.step()
         return loss, out
 
     def replay(self, batch=None):

@@ -167,6 +167,7 @@ class EMSANet(nn.Module):
         # precision): 'float32' = the reference's arithmetic (default), 'bfloat16' =
         # BASELINE configs[2] mixed-precision training, 'bfloat16' / 'float16' = configs[4] inference
         self.compute_dtype = torch.float32
+        self.loss_scaler = None      # optim.LossScaler.attach(model): float16 storage may then train
         self.set_compute_dtype(getattr(args, 'compute_dtype', 'float32'))
         # BatchNorm step counters are kept on the host (on each BatchNorm module) and written to
         # the buffers when a state_dict is taken -- of the model or of any sub-module -- by the
@@ -175,7 +176,8 @@ class EMSANet(nn.Module):
     def set_compute_dtype(self, dtype):
         """activations (and the packed conv operands) are stored as `dtype`; parameters, BatchNorm
         statistics, SE vectors, gradients of parameters and the model's outputs stay fp32, all
-        accumulation is fp32.  fp16 has no loss scaling here: inference only."""
+        accumulation is fp32.  fp16 trains only under a loss scale (`optim.LossScaler.attach`);
+        without one it is an inference mode."""
         if isinstance(dtype, str):
             dtype = {'float32': torch.float32, 'fp32': torch.float32, 'bfloat16': torch.bfloat16,
                      'bf16': torch.bfloat16, 'float16': torch.float16, 'fp16': torch.float16}[dtype]
@@ -333,7 +335,9 @@ class EMSANet(nn.Module):
                 raise _lib.EmsaError(
                     f"batch['{name}'] lives on {t.device}: the EMSANet engine only runs on an "
                     "AMD GPU (no CPU fallback)")
-        if self.compute_dtype == torch.float16 and self.training:
+        if self.compute_dtype == torch.float16 and self.training and self.loss_scaler is None:
+            # (with optim.LossScaler(...).attach(model) float16 storage trains: the backward pass
+            #  then runs under a loss scale kept on the device)
             raise _lib.EmsaError("float16 storage is an inference mode (no loss scaling); train "
                                  "in bfloat16 or float32")
         if 'rgbd' in self.args.input_modalities:

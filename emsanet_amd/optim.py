@@ -15,6 +15,9 @@ Optimizer step and learning-rate schedule of the reference's training loop on de
   flat bucket (`emsa_adam_step`) + a one-thread kernel that advances the step count and forms the
   bias corrections on the DEVICE (`emsa_adam_advance`): a step captured in a hipGraph counts its own
   replays.  `get_optimizer(args, buckets)` / `get_lr_schedule(args)`: the reference's two factories.
+* `LossScaler`: dynamic loss scaling for float16 storage (no reference counterpart: the reference has
+  no mixed precision), `torch.amp.GradScaler`'s rule with the state on the device
+  (csrc/loss_scale.hip), wrapped around either fused optimizer.
 * `one_cycle(step, ...)`: the schedule of /root/reference/emsanet/lr_scheduler.py:23-31 --
   torch's OneCycleLR(max_lr, total_steps=n_epochs, div_factor=25, pct_start=0.1,
   anneal_strategy='cos', final_div_factor=1e4), stepped once per EPOCH, INCLUDING the momentum
@@ -270,6 +273,149 @@ class FusedAdam(_FlatOptimizer):
         for dst, src in zip(self.exp_avg + self.exp_avg_sq, list(sd['exp_avg']) + list(sd['exp_avg_sq'])):
             dst.copy_(src)
         self._upload_hyper()
+
+
+class LossScaler:
+    """Dynamic loss scaling for training in float16 storage, with the rule of `torch.amp.GradScaler`
+    and its state on the DEVICE (csrc/loss_scale.hip): the overflow check, the decision to skip
+    the update and the growth / back-off of the scale are kernels that read and write 32 bytes of
+    device memory, so a step captured in a hipGraph (`graph.GraphedTrainStep(loss_scaler=...)`)
+    takes that decision at every replay and no step synchronises with the host.
+
+    usage per step:
+        scaler = LossScaler(opt).attach(model)
+        buckets.reset(); scaler.backward(loss); buckets.finish(); scaler.step()
+
+    * `backward(loss)` seeds the backward pass with the device scale as the cotangent of the
+      scalar loss: no multiply kernel, no host read.  Every gradient is then S times the true one.
+    * `step()` replaces `opt.step()`: one read-only scan per flat bucket for inf / NaN, a
+      one-thread kernel that updates the state, then the optimizer's kernels in their `_ls` forms:
+      they do nothing on a skipped step and otherwise multiply the gradients by
+      grad_scale * (1 / S), S being the scale the backward pass ran with; the new scale takes
+      effect from the next backward pass.  The scans come before any update because the decision
+      needs every bucket before any parameter moves.
+    * fp32 and bf16 models may attach a scaler too; there it is harmless (and never skips unless
+      the gradients really are non-finite).
+
+    As in `torch.amp`, a skipped step is skipped by the OPTIMIZER only: the forward pass has run,
+    so BatchNorm running statistics are updated and the Dropout2d step advances.  Adam's step
+    count does not advance.  SGD's first-step flag (`FusedSGD._first`) stays a host flag: a skipped
+    first step leaves the momentum buffers at zero, and the following step, run with first = 0,
+    forms momentum * 0 + g = g, which is the first-step rule.
+
+    What a loss scale does not repair is overflow in the FORWARD pass (an activation above 65504):
+    the loss and with it every gradient is then non-finite whatever the scale, which shows as a
+    run of skipped steps with the scale falling step after step (`state()['skipped']`).
+
+    Several ranks: `step()` runs behind `buckets.finish()` and scans the REDUCED buckets.  A
+    non-finite value on any rank is non-finite in the sum on every rank (inf + x, NaN + x), also
+    when the exchange is in bf16 (inf and NaN survive the conversion both ways), so all ranks take
+    the same decision without a collective of their own.
+
+    The growth and back-off factors and the interval are launch arguments fixed at construction;
+    `load_state_dict` restores the device state only."""
+
+    def __init__(self, optimizer, init_scale=2.0 ** 16, growth_factor=2.0, backoff_factor=0.5,
+                 growth_interval=2000):
+        init_scale, growth_factor = float(init_scale), float(growth_factor)
+        backoff_factor = float(backoff_factor)
+        if not (math.isfinite(init_scale) and init_scale > 0.0) or \
+                not math.isfinite(float(torch.tensor(init_scale, dtype=torch.float32))):
+            raise ValueError(f"init_scale must be finite and positive (in float32), got {init_scale}")
+        if not (math.isfinite(growth_factor) and growth_factor > 1.0):
+            raise ValueError(f"growth_factor must be > 1, got {growth_factor}")
+        if not 0.0 < backoff_factor < 1.0:
+            raise ValueError(f"backoff_factor must lie in (0, 1), got {backoff_factor}")
+        if int(growth_interval) != growth_interval or growth_interval < 1:
+            raise ValueError(f"growth_interval must be an integer >= 1, got {growth_interval}")
+        if not isinstance(optimizer, (FusedSGD, FusedAdam)):
+            raise TypeError("LossScaler wraps a FusedSGD or a FusedAdam")
+        self.opt = optimizer
+        self.buckets = optimizer.buckets
+        self.init_scale = init_scale
+        self.growth_factor, self.backoff_factor = growth_factor, backoff_factor
+        self.growth_interval = int(growth_interval)
+        dev = optimizer.flat_params[0].device
+        # EmsaLossScale: {float scale, inv_scale; int32 skip, growth_tracker, steps, skipped, found, -}
+        self._f = torch.zeros(8, device=dev, dtype=torch.float32)
+        self._i = self._f.view(torch.int32)
+        self._f[:2].copy_(torch.tensor([init_scale, 1.0 / init_scale], dtype=torch.float32))
+        self._scale = self._f[0]           # 0-dim view: the cotangent `backward` hands to autograd
+
+    # index of each field in the int32 view of the state
+    _SKIP, _TRACKER, _STEPS, _SKIPPED, _FOUND = 2, 3, 4, 5, 6
+
+    def attach(self, model):
+        """`model.loss_scaler = self`: EMSANet.forward then accepts float16 storage in train mode"""
+        model.loss_scaler = self
+        return self
+
+    @property
+    def device_state(self):
+        """the 32 bytes of device state as a float32 tensor of 8 (what a snapshot saves)"""
+        return self._f
+
+    def backward(self, loss):
+        """loss.backward() with the device scale as the cotangent of the (scalar, fp32) loss"""
+        if loss.numel() != 1 or loss.dtype != torch.float32:
+            raise ValueError("LossScaler.backward: a scalar float32 loss")
+        loss.backward(gradient=self._scale.view(loss.shape))
+
+    def scale_cotangents(self, cots):
+        """the cotangents of a `torch.autograd.backward(outputs, cots)` step, times the device scale
+        (one small multiply per output; no host read)"""
+        return [c * self._scale.to(c.dtype) for c in cots]
+
+    @torch.no_grad()
+    def step(self):
+        """after `buckets.finish()`: scan, state update, scaled optimizer update"""
+        opt, L, st = self.opt, _lib.lib(), Fn._stream()
+        ls = self._f.data_ptr()
+        for flat_g, ps, views in self.buckets.buckets:
+            opt._gather_gradients(ps, views)
+            check(L.emsa_nonfinite_scan(Fn._p(flat_g), flat_g.numel(), ls, st), 'emsa_nonfinite_scan')
+        check(L.emsa_loss_scale_update(ls, self.growth_factor, self.backoff_factor,
+                                       self.growth_interval, st), 'emsa_loss_scale_update')
+        if isinstance(opt, FusedSGD):
+            for (flat_g, ps, _), fp, fm in zip(self.buckets.buckets, opt.flat_params, opt.flat_momentum):
+                check(L.emsa_sgd_nesterov_ls(Fn._p(fp), Fn._p(flat_g), Fn._p(fm), fp.numel(), opt.lr,
+                                             opt.momentum, opt.weight_decay, opt._grad_scale(),
+                                             1 if opt._first else 0, Fn._p(opt._hyper), ls, st),
+                      'emsa_sgd_nesterov_ls')
+                torch.autograd.graph.increment_version(ps)
+            # (the flag needs no device twin, see the class comment: it is cleared whether or not
+            #  this first step was skipped)
+            if opt._first and (opt._hyper is None or not torch.cuda.is_current_stream_capturing()):
+                opt._first = False
+                opt._upload_hyper()
+        else:
+            check(L.emsa_adam_advance_ls(opt._hyper.data_ptr(), opt._state.data_ptr(), ls, st),
+                  'emsa_adam_advance_ls')
+            for (flat_g, ps, _), fp, m, v in zip(self.buckets.buckets, opt.flat_params, opt.exp_avg,
+                                                 opt.exp_avg_sq):
+                check(L.emsa_adam_step_ls(Fn._p(fp), Fn._p(flat_g), Fn._p(m), Fn._p(v), fp.numel(),
+                                          opt._hyper.data_ptr(), opt._state.data_ptr(), ls, st),
+                      'emsa_adam_step_ls')
+                torch.autograd.graph.increment_version(ps)
+
+    def state(self):
+        """{'scale', 'growth_tracker', 'steps', 'skipped'} -- ONE device read; this call
+        synchronises with the device (keep it out of the training loop's hot path)"""
+        host = self._f.cpu()
+        ints = host.view(torch.int32)
+        return {'scale': float(host[0]), 'growth_tracker': int(ints[self._TRACKER]),
+                'steps': int(ints[self._STEPS]), 'skipped': int(ints[self._SKIPPED])}
+
+    def state_dict(self):
+        return {'init_scale': self.init_scale, 'growth_factor': self.growth_factor,
+                'backoff_factor': self.backoff_factor, 'growth_interval': self.growth_interval,
+                'device_state': self._f.clone()}
+
+    def load_state_dict(self, sd):
+        src = sd['device_state']
+        if src.dtype != torch.float32 or src.numel() != 8:
+            raise ValueError("LossScaler.load_state_dict: device_state is 8 float32 words")
+        self._f.copy_(src)
 
 
 KNOWN_OPTIMIZERS = ('adam', 'adamw', 'radam', 'sgd')          # /root/reference/emsanet/optimizer.py:13

@@ -825,6 +825,49 @@ int emsa_adam_step(float* param, const float* grad, float* exp_avg, float* exp_a
                    const double* hyper, const double* state, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Dynamic loss scaling on the device (csrc/loss_scale.hip; training in fp16 storage).  The state
+ * lives in DEVICE memory, 32 bytes, owned by the kernels: the backward pass is seeded with `scale`
+ * as the cotangent of the loss, the scans raise `found`, the update kernel applies the rule of
+ * torch.amp.GradScaler, and the *_ls optimizer steps read `skip` and `inv_scale`.  Nothing is read
+ * back by the host: a step captured in a hipGraph takes the decision to skip at every replay.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct EmsaLossScale {
+  float scale;              /* what the NEXT backward pass multiplies the loss by                  */
+  float inv_scale;          /* 1 / the scale the LAST backward pass ran with: this step's update   */
+  int32_t skip;             /* 1: the last scanned step had a non-finite gradient, nothing moves   */
+  int32_t growth_tracker;   /* clean steps since the last growth or back-off                       */
+  int32_t steps;            /* updates of this state (skipped ones included)                       */
+  int32_t skipped;          /* of which skipped                                                    */
+  int32_t found;            /* raised by emsa_nonfinite_scan, cleared by emsa_loss_scale_update    */
+  int32_t reserved;
+} EmsaLossScale;
+/* state->found = 1 if any of the n floats at grad (4-byte aligned; read-only) has all exponent bits
+ * set (+-inf, every NaN); never writes 0.  float4 loads over the 16-byte aligned body.            */
+int emsa_nonfinite_scan(const float* grad, int64_t n, EmsaLossScale* state, void* stream);
+/* one thread, once per step behind the scans of ALL buckets:
+ *   inv_scale = 1 / scale; steps += 1
+ *   found:  scale *= backoff_factor; growth_tracker = 0; skip = 1; skipped += 1
+ *   else:   skip = 0; growth_tracker += 1; at growth_interval: scale *= growth_factor unless that is
+ *           non-finite, growth_tracker = 0
+ *   found = 0                                                                                     */
+int emsa_loss_scale_update(EmsaLossScale* state, float growth_factor, float backoff_factor,
+                           int32_t growth_interval, void* stream);
+/* emsa_sgd_nesterov (hyper == NULL) / emsa_sgd_nesterov_dev (hyper != NULL) under a loss scale:
+ * skip == 1 leaves param and momentum_buf untouched; else grad is multiplied by
+ * grad_scale * inv_scale (one factor, formed first) where the plain forms multiply by grad_scale --
+ * for a power-of-two scale S the step on S g equals the plain step on g bit for bit.            */
+int emsa_sgd_nesterov_ls(float* param, const float* grad, float* momentum_buf, int64_t n, float lr,
+                         float momentum, float weight_decay, float grad_scale, int32_t first_step,
+                         const float* hyper, const EmsaLossScale* state, void* stream);
+/* emsa_adam_advance / emsa_adam_step under a loss scale: skip == 1 leaves the step count, both
+ * moments and the parameters untouched                                                            */
+int emsa_adam_advance_ls(const double* hyper, double* adam_state, const EmsaLossScale* state,
+                         void* stream);
+int emsa_adam_step_ls(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                      const double* hyper, const double* adam_state, const EmsaLossScale* state,
+                      void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Inference output packing (csrc/export.hip): the `scannet-semantic`, `scannet-instance`,
  * `scannet-panoptic` and `mapping` formats of /root/reference/inference_dataset.py:139-552, formed on
  * the device from the post-processed prediction, so that only the packed bytes go to the host.
