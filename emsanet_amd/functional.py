@@ -594,6 +594,20 @@ def nbt_half_block(xs, wfa, bias_a, wfb, bias_b, scales, shifts, residuals, act=
     return tuple(outs)
 
 
+def _pair_refused(xs, ws, biases, scales, shifts, residuals):
+    """what no twin launch takes: a missing weight form, operands that differ in dtype / shape / ld,
+    fp32 storage, weights of another dtype, a bias / scale / shift / residual only one side has"""
+    x0, x1 = xs
+    if ws[0] is None or ws[1] is None or x0.dtype != x1.dtype or x0.shape != x1.shape:
+        return True
+    if dt(x0) == 0 or ws[0].dtype != x0.dtype or ws[1].dtype != x0.dtype or ld_of(x0) != ld_of(x1):
+        return True
+    r0, r1 = residuals
+    if (r0 is None) != (r1 is None) or (r0 is not None and ld_of(r0) != ld_of(r1)):
+        return True
+    return any((pr[0] is None) != (pr[1] is None) for pr in (biases, scales, shifts))
+
+
 def conv_fwd_pair(xs, wfrags, spec, biases=(None, None), scales=(None, None), shifts=(None, None),
                   residuals=(None, None), act=ACT_NONE):
     """two forward convs of ONE geometry (the rgb | depth encoders, the semantic | instance decoders)
@@ -601,21 +615,10 @@ def conv_fwd_pair(xs, wfrags, spec, biases=(None, None), scales=(None, None), sh
     (out0, out1), or None where that kernel does not take the pair (other dtype / geometry / strides)
     -- the caller then launches the two convs one by one.  Each result is bit-identical to its own
     conv_fwd(..., wfrag=...) launch."""
-    x0, x1 = xs
-    if wfrags[0] is None or wfrags[1] is None or x0.dtype != x1.dtype or x0.shape != x1.shape:
+    if _pair_refused(xs, wfrags, biases, scales, shifts, residuals):
         return None
-    code = dt(x0)
-    if code == 0 or wfrags[0].dtype != x0.dtype or wfrags[1].dtype != x0.dtype:
-        return None
+    (x0, x1), (r0, r1), code = xs, residuals, dt(xs[0])
     n, c, h, w = x0.shape
-    if ld_of(x0) != ld_of(x1):
-        return None
-    r0, r1 = residuals
-    if (r0 is None) != (r1 is None) or (r0 is not None and ld_of(r0) != ld_of(r1)):
-        return None
-    for pr in (biases, scales, shifts):
-        if (pr[0] is None) != (pr[1] is None):
-            return None
     oh, ow = spec.out_hw(h, w)
     g = spec.geom_fwd(n, h, w, ld_of(x0), spec.cout)
     if not rs_supported(code, g):
@@ -634,20 +637,11 @@ def conv_igemm_pair(xs, wps, spec, biases=(None, None), scales=(None, None), shi
                     residuals=(None, None), act=ACT_NONE):
     """conv_fwd_pair for the convs the implicit GEMM runs (strided, 1x1, 3x3; 16-bit storage):
     emsa_conv_igemm_pair_t, tap-split where the single launch would be.  (out0, out1) or None"""
-    x0, x1 = xs
-    if wps[0] is None or wps[1] is None or x0.dtype != x1.dtype or x0.shape != x1.shape:
+    if _pair_refused(xs, wps, biases, scales, shifts, residuals):
         return None
-    code = dt(x0)
-    if code == 0 or wps[0].dtype != x0.dtype or wps[1].dtype != x0.dtype or ld_of(x0) != ld_of(x1):
-        return None
-    r0, r1 = residuals
-    if (r0 is None) != (r1 is None) or (r0 is not None and ld_of(r0) != ld_of(r1)):
-        return None
-    for pr in (biases, scales, shifts):
-        if (pr[0] is None) != (pr[1] is None):
-            return None
     if os.environ.get('EMSA_CONVH_PF', '0') not in ('', '0'):
         return None
+    (x0, x1), (r0, r1), code = xs, residuals, dt(xs[0])
     n, c, h, w = x0.shape
     oh, ow = spec.out_hw(h, w)
     g = spec.geom_fwd(n, h, w, ld_of(x0), spec.cout)

@@ -7,7 +7,10 @@ per NonBottleneck1D block (4 MFMA convs + 2 BatchNorms + Dropout2d + residual, h
 backward with the ReLU masks and the residual add fused into the data-gradient epilogues), one
 per conv+BN+act, per SE fusion, per learned upsampling ...  Every Function only sequences calls
 into libemsanet_hip.so (emsanet_amd/functional.py); autograd is used for graph bookkeeping only.
+What travels between these host functions is a named record: _ConvBN, _NBtSaved, _WgradJob.
 """
+import collections
+import contextlib
 import os
 
 import torch
@@ -618,11 +621,16 @@ class BNRT:
         return s, t
 
 
+# _conv_bn_forward's result.  y: the conv's raw output; mask: bit mask of out > 0 for the backward
+# pass (None without ReLU); affine: the BatchNorm as (scale, shift) with batch statistics, else None
+# (a data gradient with the fused BatchNorm reduction recomputes the ReLU mask from it)
+_ConvBN = collections.namedtuple('_ConvBN', 'out y mean invstd mask affine')
+
+
 def _conv_bn_forward(x, crt, brt, act, drop=None, residual=None, wino_bits=False, res_affine=None):
-    """conv (+bias) -> BN (batch or frozen statistics) -> *drop -> +residual -> act.
-    returns out, y_raw, mean, invstd, relu_mask (bit mask of out > 0 for the backward pass, or
-    None without ReLU; wino_bits: in the Winograd epilogue's layout, Fn.bn_act).  res_affine: the
-    residual is `residual * scale + shift` (Fn.bn_act)"""
+    """conv (+bias) -> BN (batch or frozen statistics) -> *drop -> +residual -> act -> _ConvBN.
+    wino_bits: the mask in the Winograd epilogue's layout (Fn.bn_act).  res_affine: the residual
+    is `residual * scale + shift` (Fn.bn_act)"""
     bias = crt.conv.bias.detach() if crt.conv.bias is not None else None
     if brt.batch_stats():
         y, stats = crt.forward(x, bias=bias, want_stats=True)
@@ -632,11 +640,7 @@ def _conv_bn_forward(x, crt, brt, act, drop=None, residual=None, wino_bits=False
     scale, shift, mean, invstd = brt.forward_stats(stats, count)
     out, mask = Fn.bn_act(y, scale, shift, drop, residual, act, want_mask=True, wino_bits=wino_bits,
                           res_affine=res_affine)
-    # (the affine form travels with the statistics: a data gradient with the fused BatchNorm
-    #  reduction recomputes the ReLU mask from it)
-    if brt.batch_stats():                # (`mean` is this call's own tensor, not the running buffer)
-        mean._emsa_affine = (scale, shift)
-    return out, y, mean, invstd, mask
+    return _ConvBN(out, y, mean, invstd, mask, (scale, shift) if brt.batch_stats() else None)
 
 
 def _bn_targets(brt):
@@ -686,17 +690,9 @@ class _Deferred:
         self.index, self.which = index, which
 
 
-_in_side = False
-
-
-class _SideGuard:
-    def __enter__(self):
-        global _in_side
-        _in_side = True
-
-    def __exit__(self, *exc):
-        global _in_side
-        _in_side = False
+# a deferred weight gradient: conv input, output gradient, ConvRT, the flat-bucket views dw / dbias go
+# to (or None), the BatchNorm + ReLU the forward folded into the conv's loader (or None)
+_WgradJob = collections.namedtuple('_WgradJob', 'x dy crt tw tb in_affine')
 
 
 def _wgrad_now(x, dy, crt, tw, tb, in_affine=None):
@@ -710,33 +706,62 @@ def _wgrad_now(x, dy, crt, tw, tb, in_affine=None):
     return dw, db
 
 
-def _flush_wgrads(defer, grads):
-    """launch the deferred weight gradients -- convs of equal channel counts together in one
-    multi-job launch (Fn.conv_wgrad_multi; the four convs of an NBt1D block), the rest one by one --
-    and put the results in the places their `_Deferred` placeholders hold in `grads`"""
-    if not defer:
+def _launch_wgrads(jobs):
+    """the weight gradients of `jobs` -> [(dw, db), ...]: convs of equal channel counts together in
+    one multi-job launch (Fn.conv_wgrad_multi; the four convs of an NBt1D block), the rest one by one"""
+    res = [None] * len(jobs)
+    groups = {}
+    for i, job in enumerate(jobs):
+        ok = (job.in_affine is None or job.x.dtype != torch.float32) and \
+            Fn.wgrad_multi_eligible(job.x, job.crt.spec)
+        groups.setdefault((job.crt.spec.cin, job.crt.spec.cout) if ok else ('single', i), []).append(i)
+    for idx in groups.values():
+        for k in range(0, len(idx), Fn.WGRAD_MULTI_MAX):
+            part = idx[k:k + Fn.WGRAD_MULTI_MAX]
+            out = None
+            if len(part) >= 2:
+                out = Fn.conv_wgrad_multi([(j.x, j.dy, j.crt.spec, j.crt.conv.weight, j.tw, j.tb,
+                                            j.crt.conv.bias is not None, j.in_affine)
+                                           for j in (jobs[i] for i in part)])
+            if out is None:
+                for i in part:
+                    res[i] = _wgrad_now(*jobs[i])
+            else:
+                for i, (dw, db) in zip(part, out):
+                    tw = jobs[i].tw
+                    res[i] = (tw if tw is not None and dw.data_ptr() == tw.data_ptr() else dw, db)
+    return res
+
+
+def _flush_wgrads(jobs, grads):
+    """launch the deferred weight gradients (`_launch_wgrads`; with EMSA_WGRAD_STREAM on the side
+    stream) and put the results in the places their `_Deferred` placeholders hold in `grads`"""
+    if not jobs:
         return grads
-    if WGRAD_STREAM and defer[0][0].is_cuda and not _in_side:
+    side = None
+    if WGRAD_STREAM and jobs[0].x.is_cuda:
         cur = torch.cuda.current_stream()
         side = _wgrad_side(cur)
         side.wait_stream(cur)
-        with torch.cuda.stream(side), _SideGuard():
-            out = _flush_wgrads(defer, grads)
-        for x, dy, *_ in defer:                 # (the caching allocator must not recycle them early)
-            x.record_stream(side)
-            dy.record_stream(side)
+    with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
+        res = _launch_wgrads(jobs)
+    out = [res[g.index][g.which] if isinstance(g, _Deferred) else g for g in grads]
+    if side is not None:
+        for job in jobs:                        # (the caching allocator must not recycle them early)
+            job.x.record_stream(side)
+            job.dy.record_stream(side)
         # The join may wait for the end of the backward pass only where nobody reads these gradients
         # before: every one of them written into a bucket view of MANUAL buckets (no autograd hooks: the
         # caller reduces after backward).  Otherwise AccumulateGrad (adding into an existing .grad) or a
         # hook-driven bucket all-reduce would consume them while the side stream still writes (ADVICE
         # r5): join right here, and tell the allocator which stream the fresh tensors are used on.
         def _manual(job):
-            slot = getattr(job[2].conv.weight, '_emsa_grad_slot', None)
-            bias = job[2].conv.bias
+            slot = getattr(job.crt.conv.weight, '_emsa_grad_slot', None)
+            bias = job.crt.conv.bias
             bslot = getattr(bias, '_emsa_grad_slot', None) if bias is not None else slot
-            return (job[3] is not None and slot is not None and getattr(slot[1], 'manual', False) and
-                    (bias is None or (job[4] is not None and bslot is not None)))
-        if all(_manual(job) for job in defer):
+            return (job.tw is not None and slot is not None and getattr(slot[1], 'manual', False) and
+                    (bias is None or (job.tb is not None and bslot is not None)))
+        if all(_manual(job) for job in jobs):
             if not _wgrad_pending:
                 torch.autograd.Variable._execution_engine.queue_callback(_join_wgrad_streams)
             if side not in _wgrad_pending:
@@ -746,40 +771,18 @@ def _flush_wgrads(defer, grads):
             for g in out:
                 if torch.is_tensor(g):
                     g.record_stream(cur)
-        return out
-    res = [None] * len(defer)
-    groups = {}
-    for i, job in enumerate(defer):
-        ok = (job[5] is None or job[0].dtype != torch.float32) and \
-            Fn.wgrad_multi_eligible(job[0], job[2].spec)
-        groups.setdefault((job[2].spec.cin, job[2].spec.cout) if ok else ('single', i), []).append(i)
-    for idx in groups.values():
-        for k in range(0, len(idx), Fn.WGRAD_MULTI_MAX):
-            part = idx[k:k + Fn.WGRAD_MULTI_MAX]
-            out = None
-            if len(part) >= 2:
-                out = Fn.conv_wgrad_multi([(defer[i][0], defer[i][1], defer[i][2].spec,
-                                            defer[i][2].conv.weight, defer[i][3], defer[i][4],
-                                            defer[i][2].conv.bias is not None, defer[i][5])
-                                           for i in part])
-            if out is None:
-                for i in part:
-                    x, dy, crt, tw, tb, aff = defer[i]
-                    res[i] = _wgrad_now(x, dy, crt, tw, tb, aff)
-            else:
-                for i, (dw, db) in zip(part, out):
-                    tw = defer[i][3]
-                    res[i] = (tw if tw is not None and dw.data_ptr() == tw.data_ptr() else dw, db)
-    return [res[g.index][g.which] if isinstance(g, _Deferred) else g for g in grads]
+    return out
 
 
 def _conv_backward(x, dy, crt, need_dx, mask_src=None, residual=None, mask_bits=None, bnb=None,
                    in_affine=None, defer=None, res_bits=None):
-    """-> dx (or None), dw (OIHW), dbias (or None); with bnb = (t, (scale, shift), mean, invstd) of
-    the BatchNorm+ReLU in front of the conv: -> dx, dw, dbias, (partial, rows) or None -- dx then
-    already carries that ReLU's mask (ConvRT.dgrad_bnb).  in_affine: the forward folded that
+    """-> dx (or None), dw (OIHW), dbias (or None), bn_rows.  bnb = (t, (scale, shift), mean, invstd)
+    of the BatchNorm+ReLU in front of the conv: bn_rows is (partial, rows) where the data gradient
+    carries that BatchNorm's backward reduction -- dx then already has that ReLU's mask
+    (ConvRT.dgrad_bnb) -- and None otherwise (always without bnb).  in_affine: the forward folded that
     BatchNorm + ReLU into the conv's loader (x = the BatchNorm's INPUT).  defer: a list -- the
-    weight gradient is not launched here but queued (`_flush_wgrads`), dw / dbias are placeholders.
+    weight gradient is not launched here but queued as a _WgradJob (`_flush_wgrads`), dw / dbias
+    are `_Deferred` placeholders.
     res_bits: `residual` is unmasked, its ReLU mask travels as bits (ConvRT.dgrad_takes_res_bits)"""
     conv = crt.conv
     _trace_grad(conv, dy)
@@ -790,7 +793,7 @@ def _conv_backward(x, dy, crt, need_dx, mask_src=None, residual=None, mask_bits=
     half = dy.dtype != torch.float32
     if defer is not None and (WGRAD_STREAM or ((in_affine is None or half) and
                                                Fn.wgrad_multi_eligible(x, crt.spec))):
-        defer.append((x, dy, crt, tw, tb, in_affine))
+        defer.append(_WgradJob(x, dy, crt, tw, tb, in_affine))
         dw, db = _Deferred(len(defer) - 1, 0), _Deferred(len(defer) - 1, 1)
     else:
         dw, db = _wgrad_now(x, dy, crt, tw, tb, in_affine)
@@ -813,7 +816,7 @@ def _conv_backward(x, dy, crt, need_dx, mask_src=None, residual=None, mask_bits=
     elif need_dx:
         dx = crt.dgrad(dy, x.shape[2:], mask_src=mask_src, residual=residual,
                        mask_bits=mask_bits)
-    return dx, dw, db
+    return dx, dw, db, None
 
 
 # ---------------------------------------------------------------------------------------------
@@ -842,6 +845,16 @@ class NBt1DRT:
         return ps
 
 
+# what an NBt1D block keeps for its backward pass besides its input.  y1 .. y4: the four convs' raw
+# outputs (y1, y3 after their ReLU); a2 = relu(bn1(y2)), None where bn1 is folded into conv3x1_2's
+# loader; yd: the shortcut conv's output (or None); m* / is*: mean, invstd of bn1, bn2, the shortcut's
+# BatchNorm; aff1: bn1 as (scale, shift) with batch statistics, else None; k1, k2: ReLU bit masks of
+# the two BatchNorm outputs (the block output itself is not kept); q1, q3: those of y1, y3 (None when
+# the layer does not run on the Winograd kernel)
+_NBtSaved = collections.namedtuple(
+    '_NBtSaved', 'y1 y2 a2 y3 y4 yd m1 is1 m2 is2 md isd k1 k2 q1 q3 aff1')
+
+
 class NBt1DFunction(Function):
     """conv3x1+b,ReLU -> conv1x3+b,BN,ReLU -> conv3x1+b,ReLU -> conv1x3+b,BN -> Dropout2d
     -> + identity -> ReLU   (reference block: SURVEY.md §8 a3)."""
@@ -850,32 +863,30 @@ class NBt1DFunction(Function):
     def forward(ctx, x, rt, drop, *params):
         x = Fn.as_act(x, dense=True)
         b = lambda c: c.conv.bias.detach()   # noqa: E731
-        # y1, y3 = relu(conv): their ReLU masks go to the backward pass as bits (q1, q3; None when
-        # the layer does not run on the Winograd kernel)
         y1, q1 = rt.c31_1.forward(x, bias=b(rt.c31_1), act=ACT_RELU, want_relu_bits=True)
-        fold = rt.bn1.batch_stats() and rt.c31_2.folds_input_bn(y1)
-        if fold:
+        bn1_folded = rt.bn1.batch_stats() and rt.c31_2.folds_input_bn(y1)
+        if bn1_folded:
             # bn1's normalise + ReLU happens in the loaders of conv3x1_2 (here) and of its weight
             # gradient; a2 = relu(bn1(y2)) is never written, no ReLU bit mask either (the data
             # gradient recomputes the decisions from y2)
             y2, stats = rt.c13_1.forward(y1, bias=b(rt.c13_1), want_stats=True)
             scale, shift, m1, is1 = rt.bn1.forward_stats(stats, y2.shape[0] * y2.shape[2] * y2.shape[3])
-            m1._emsa_affine = (scale, shift)
+            aff1 = (scale, shift)
             a2 = k1 = None
             y3, q3 = rt.c31_2.forward(y2, bias=b(rt.c31_2), act=ACT_RELU, want_relu_bits=True,
-                                      in_affine=(scale, shift))
+                                      in_affine=aff1)
         else:
-            a2, y2, m1, is1, k1 = _conv_bn_forward(y1, rt.c13_1, rt.bn1, ACT_RELU)
+            a2, y2, m1, is1, k1, aff1 = _conv_bn_forward(y1, rt.c13_1, rt.bn1, ACT_RELU)
             y3, q3 = rt.c31_2.forward(a2, bias=b(rt.c31_2), act=ACT_RELU, want_relu_bits=True)
         aff_d = None
         if rt.cds is not None and rt.bnds.batch_stats() and rt.bn2.batch_stats() and Fn.idn_fold(y3):
             # the shortcut's normalise happens inside bn2's pass (Fn.idn_fold): idn is never written
             yd, stats = rt.cds.forward(x, want_stats=True)
             sd, td, md, isd = rt.bnds.forward_stats(stats, yd.shape[0] * yd.shape[2] * yd.shape[3])
-            md._emsa_affine = aff_d = (sd, td)
+            aff_d = (sd, td)
             idn = yd
         elif rt.cds is not None:
-            idn, yd, md, isd, _ = _conv_bn_forward(x, rt.cds, rt.bnds, ACT_NONE)
+            idn, yd, md, isd, _, _ = _conv_bn_forward(x, rt.cds, rt.bnds, ACT_NONE)
         else:
             idn, yd, md, isd = x, None, None, None
         # k2 in the layout conv3x1_1's data gradient (bnds' backward in a down-sampling block) reads:
@@ -886,17 +897,15 @@ class NBt1DFunction(Function):
                 (rt.cds is not None or (rt.c31_1.wino and not rt.c31_1.wino2d))
             if not wbits:
                 Fn._dres_fell_back()
-        out, y4, m2, is2, k2 = _conv_bn_forward(y3, rt.c13_2, rt.bn2, ACT_RELU, drop=drop,
-                                                residual=idn, wino_bits=wbits, res_affine=aff_d)
+        out, y4, m2, is2, k2, _ = _conv_bn_forward(y3, rt.c13_2, rt.bn2, ACT_RELU, drop=drop,
+                                                   residual=idn, wino_bits=wbits, res_affine=aff_d)
         if MASK_TRACE is not None:
             a2t = a2 if a2 is not None else Fn.bn_act(y2, scale, shift, None, None, ACT_RELU)
             for tag, t in (('nbt.y1', y1), ('nbt.a2', a2t), ('nbt.y3', y3), ('nbt.out', out)):
                 _trace_mask(tag, t)
         ctx.rt, ctx.drop = rt, drop
         ctx.save_for_backward(x)
-        # the ReLU masks of the two BatchNorm outputs travel as bit masks (k1, k2): the block
-        # output itself is not kept for the backward pass
-        ctx.saved = (y1, y2, a2, y3, y4, yd, m1, is1, m2, is2, md, isd, k1, k2, q1, q3)
+        ctx.saved = _NBtSaved(y1, y2, a2, y3, y4, yd, m1, is1, m2, is2, md, isd, k1, k2, q1, q3, aff1)
         ctx.bn_train = (rt.bn1.batch_stats(), rt.bn2.batch_stats(),
                         rt.bnds.batch_stats() if rt.bnds is not None else False)
         return out
@@ -907,67 +916,66 @@ class NBt1DFunction(Function):
     def backward(ctx, dout):
         rt, drop = ctx.rt, ctx.drop
         (x,) = ctx.saved_tensors
-        y1, y2, a2, y3, y4, yd, m1, is1, m2, is2, md, isd, k1, k2, q1, q3 = ctx.saved
+        s = ctx.saved
         ctx.saved = None
         dout = Fn.as_act(dout, dense=True)
         t1, t2, tds = ctx.bn_train
         need_dx = ctx.needs_input_grad[0]
         defer = []           # the block's weight gradients: launched together at the end
+        bn1_folded = s.a2 is None        # the forward folded bn1 into conv3x1_2's loader
 
         # out = relu(bn2(y4)*drop + idn)
         # (k2 in the Winograd layout: dres = dout * k2 is not stored, its one reader forms it)
-        fold = getattr(k2, '_emsa_wbits', False)
-        if fold and rt.cds is None and need_dx and \
-                not rt.c31_1.dgrad_takes_res_bits(y1, x.shape[2:], dout):
-            fold = False
+        dres_folded = getattr(s.k2, '_emsa_wbits', False)
+        if dres_folded and rt.cds is None and need_dx and \
+                not rt.c31_1.dgrad_takes_res_bits(s.y1, x.shape[2:], dout):
+            dres_folded = False
             Fn._dres_fell_back()
-        dy4, dres, dg2, db2 = Fn.bn_bwd(dout, k2, y4, rt.bn2.bn.weight.detach(), m2, is2, drop,
-                                        ACT_RELU, t2, want_dres=not fold, **_bn_targets(rt.bn2))
+        dy4, dres, dg2, db2 = Fn.bn_bwd(dout, s.k2, s.y4, rt.bn2.bn.weight.detach(), s.m2, s.is2, drop,
+                                        ACT_RELU, t2, want_dres=not dres_folded, **_bn_targets(rt.bn2))
         # conv1x3_2 (input y3 = relu(.)): ReLU mask fused into the dgrad epilogue
-        dz3, dw4, dbias4 = _conv_backward(y3, dy4, rt.c13_2, True, mask_src=y3, mask_bits=q3,
-                                          defer=defer)
+        dz3, dw4, dbias4, _ = _conv_backward(s.y3, dy4, rt.c13_2, True, mask_src=s.y3, mask_bits=s.q3,
+                                             defer=defer)
         # conv3x1_2 (input a2 = relu(bn1(y2)))
         # the data gradient's epilogue applies bn1's ReLU mask and emits bn1's backward sums (one
         # pass over da2 and y2 less); falls back to the separate reduction pass
-        aff1 = getattr(m1, '_emsa_affine', None)
-        if a2 is None:                    # folded forward: the conv's input is relu(bn1(y2))
-            da2, dw3, dbias3, fused = _conv_backward(y2, dz3, rt.c31_2, True,
-                                                     bnb=(y2, aff1, m1, is1), in_affine=aff1,
-                                                     defer=defer if y2.dtype != torch.float32 else None)
+        bnb = (s.y2, s.aff1, s.m1, s.is1)
+        if bn1_folded:                    # the conv's input is relu(bn1(y2))
+            da2, dw3, dbias3, rows = _conv_backward(s.y2, dz3, rt.c31_2, True, bnb=bnb, in_affine=s.aff1,
+                                                    defer=defer if s.y2.dtype != torch.float32 else None)
         else:
-            da2, dw3, dbias3, fused = _conv_backward(a2, dz3, rt.c31_2, True,
-                                                     bnb=(y2, aff1, m1, is1), defer=defer)
-        if fused is not None:
-            dy2, dg1, db1 = Fn.bn_bwd_from_rows(da2, y2, rt.bn1.bn.weight.detach(), m1, is1,
-                                                fused[0], fused[1], t1, **_bn_targets(rt.bn1))
-        elif a2 is None:
+            da2, dw3, dbias3, rows = _conv_backward(s.a2, dz3, rt.c31_2, True, bnb=bnb, defer=defer)
+        if rows is not None:
+            dy2, dg1, db1 = Fn.bn_bwd_from_rows(da2, s.y2, rt.bn1.bn.weight.detach(), s.m1, s.is1,
+                                                rows[0], rows[1], t1, **_bn_targets(rt.bn1))
+        elif bn1_folded:
             # 16-bit fold: no a2, no bit mask -- the passes recompute the decisions from y2
-            dy2, dg1, db1 = Fn.bn_bwd_aff(da2, y2, rt.bn1.bn.weight.detach(), m1, is1, aff1,
+            dy2, dg1, db1 = Fn.bn_bwd_aff(da2, s.y2, rt.bn1.bn.weight.detach(), s.m1, s.is1, s.aff1,
                                           **_bn_targets(rt.bn1))
         else:
-            dy2, _, dg1, db1 = Fn.bn_bwd(da2, k1, y2, rt.bn1.bn.weight.detach(), m1, is1, None,
+            dy2, _, dg1, db1 = Fn.bn_bwd(da2, s.k1, s.y2, rt.bn1.bn.weight.detach(), s.m1, s.is1, None,
                                          ACT_RELU, t1, want_dres=False, **_bn_targets(rt.bn1))
-        dz1, dw2, dbias2 = _conv_backward(y1, dy2, rt.c13_1, True, mask_src=y1, mask_bits=q1,
-                                          defer=defer)
-        grads = []
+        dz1, dw2, dbias2, _ = _conv_backward(s.y1, dy2, rt.c13_1, True, mask_src=s.y1, mask_bits=s.q1,
+                                             defer=defer)
         if rt.cds is None:
             # identity skip: dx = dgrad(conv3x1_1) + dres, add fused into the epilogue
-            if fold:
-                dx, dw1, dbias1 = _conv_backward(x, dz1, rt.c31_1, need_dx, residual=dout,
-                                                 res_bits=k2, defer=defer)
+            if dres_folded:
+                dx, dw1, dbias1, _ = _conv_backward(x, dz1, rt.c31_1, need_dx, residual=dout,
+                                                    res_bits=s.k2, defer=defer)
             else:
-                dx, dw1, dbias1 = _conv_backward(x, dz1, rt.c31_1, need_dx, residual=dres, defer=defer)
+                dx, dw1, dbias1, _ = _conv_backward(x, dz1, rt.c31_1, need_dx, residual=dres,
+                                                    defer=defer)
         else:
-            if fold:           # the masked incoming gradient: dout with k2 as its ReLU mask
-                dyd, _, dgd, dbd = Fn.bn_bwd(dout, k2, yd, rt.bnds.bn.weight.detach(), md, isd,
+            if dres_folded:    # the masked incoming gradient: dout with k2 as its ReLU mask
+                dyd, _, dgd, dbd = Fn.bn_bwd(dout, s.k2, s.yd, rt.bnds.bn.weight.detach(), s.md, s.isd,
                                              None, ACT_RELU, tds, want_dres=False,
                                              **_bn_targets(rt.bnds))
             else:
-                dyd, _, dgd, dbd = Fn.bn_bwd(dres, None, yd, rt.bnds.bn.weight.detach(), md, isd,
+                dyd, _, dgd, dbd = Fn.bn_bwd(dres, None, s.yd, rt.bnds.bn.weight.detach(), s.md, s.isd,
                                              None, ACT_NONE, tds, want_dres=False,
                                              **_bn_targets(rt.bnds))
-            dxd, dwd, _ = _conv_backward(x, dyd, rt.cds, need_dx)
-            dx, dw1, dbias1 = _conv_backward(x, dz1, rt.c31_1, need_dx, residual=dxd, defer=defer)
+            dxd, dwd, _, _ = _conv_backward(x, dyd, rt.cds, need_dx)
+            dx, dw1, dbias1, _ = _conv_backward(x, dz1, rt.c31_1, need_dx, residual=dxd, defer=defer)
         grads = [dw1, dbias1, dw2, dbias2, dg1, db1, dw3, dbias3, dw4, dbias4, dg2, db2]
         if rt.cds is not None:
             grads += [dwd, dgd, dbd]
@@ -995,37 +1003,14 @@ def _half(xs, cas, cbs, bns, residuals):
                              [f[0] for f in folds], [f[1] for f in folds], residuals, ACT_RELU)
 
 
-def nbt1d_eval(x, rt):
-    """no-grad / eval fast path: both BatchNorms folded into the conv epilogues (4 launches; 2 where
-    the fused half-block kernel takes the map: small-batch 16-bit inference at C = 64 / 128)."""
-    b = lambda c: c.conv.bias.detach()   # noqa: E731
-    h1, h2 = _half_block_specs(rt)
-    if h1 and Fn.half_block_ok(x, rt.c31_1.spec.cin):
-        (a2,) = _half([x], [rt.c31_1], [rt.c13_1], [rt.bn1], [None])
-    else:
-        y1 = rt.c31_1.forward(x, bias=b(rt.c31_1), act=ACT_RELU)
-        s1, t1 = rt.bn1.folded()
-        a2 = rt.c13_1.forward(y1, bias=b(rt.c13_1), scale=s1, shift=t1, act=ACT_RELU)
-    if rt.cds is not None:
-        sd, td = rt.bnds.folded()
-        idn = rt.cds.forward(x, scale=sd, shift=td)
-    else:
-        idn = x
-    if h2 and Fn.half_block_ok(a2, rt.c31_2.spec.cin) and Fn.ld_of(idn) == idn.shape[1]:
-        return _half([a2], [rt.c31_2], [rt.c13_2], [rt.bn2], [idn])[0]
-    y3 = rt.c31_2.forward(a2, bias=b(rt.c31_2), act=ACT_RELU)
-    s2, t2 = rt.bn2.folded()
-    return rt.c13_2.forward(y3, bias=b(rt.c13_2), scale=s2, shift=t2, residual=idn, act=ACT_RELU)
-
-
-def _conv_pair(xa, xb, ca, cb, **kw):
-    """the same conv layer of two twin modules on their two inputs: one twin launch -- of the
-    register-stationary kernel where it takes the geometry (Fn.conv_fwd_pair), else of the implicit
-    GEMM (Fn.conv_igemm_pair) -- or two launches (fp32 storage).
-    kw: per-operand pairs (bias=, scale=, shift=, residual=) and act="""
-    act = kw.pop('act', ACT_NONE)
-    pr = {k: kw.get(k, (None, None)) for k in ('bias', 'scale', 'shift', 'residual')}
-    if ca.spec_key() == cb.spec_key():
+def _convs(xs, crts, act=ACT_NONE, **kw):
+    """the same conv layer of 1 or 2 (twin) modules on their inputs -> list of outputs.  Two: one
+    twin launch -- of the register-stationary kernel where it takes the geometry (Fn.conv_fwd_pair),
+    else of the implicit GEMM (Fn.conv_igemm_pair) -- or two launches (fp32 storage).
+    kw: per-entry lists of operands (bias=, scale=, shift=, residual=)"""
+    pr = {k: kw.get(k) or [None] * len(xs) for k in ('bias', 'scale', 'shift', 'residual')}
+    if len(xs) == 2 and crts[0].spec_key() == crts[1].spec_key():
+        (xa, xb), (ca, cb) = xs, crts
         r = Fn.conv_fwd_pair((xa, xb), (ca.frag(xa.dtype), cb.frag(xb.dtype)), ca.spec,
                              biases=pr['bias'], scales=pr['scale'], shifts=pr['shift'],
                              residuals=pr['residual'], act=act)
@@ -1034,9 +1019,9 @@ def _conv_pair(xa, xb, ca, cb, **kw):
                                    biases=pr['bias'], scales=pr['scale'], shifts=pr['shift'],
                                    residuals=pr['residual'], act=act)
         if r is not None:
-            return r
-    one = lambda i, x, c: c.forward(x, act=act, **{k: v[i] for k, v in pr.items() if v[i] is not None})  # noqa: E731
-    return one(0, xa, ca), one(1, xb, cb)
+            return list(r)
+    return [c.forward(x, act=act, **{k: v[i] for k, v in pr.items() if v[i] is not None})
+            for i, (x, c) in enumerate(zip(xs, crts))]
 
 
 def conv_bn_act_eval_pair(xa, xb, ma, mb):
@@ -1045,45 +1030,57 @@ def conv_bn_act_eval_pair(xa, xb, ma, mb):
     if ma.act != mb.act:
         raise _lib.EmsaError("twin ConvNormAct layers differ in their activation")
     (sa, ta), (sb, tb) = ma._brt.folded(), mb._brt.folded()
-    return _conv_pair(xa, xb, ma._crt, mb._crt, scale=(sa, sb), shift=(ta, tb), act=ma.act)
+    return tuple(_convs([xa, xb], [ma._crt, mb._crt], scale=[sa, sb], shift=[ta, tb], act=ma.act))
+
+
+def _nbt1d_eval(xs, rts):
+    """the eval sequence of an NBt1D block over 1 tensor set, or over 2: the SAME block of two twin
+    networks in lockstep, every conv both blocks share a geometry for as one twin launch (`_convs`).
+    A fused half-block launch (`_half`) takes all tensor sets or none."""
+    if any((r.cds is None) != (rts[0].cds is None) for r in rts):
+        raise _lib.EmsaError("twin NBt1D blocks differ in their skip path")
+    bias = lambda cs: [c.conv.bias.detach() for c in cs]   # noqa: E731
+    same = lambda cs: all(c.spec_key() == cs[0].spec_key() for c in cs)   # noqa: E731
+    halves = [_half_block_specs(r) for r in rts]
+    c31_1, c13_1 = [r.c31_1 for r in rts], [r.c13_1 for r in rts]
+    c31_2, c13_2 = [r.c31_2 for r in rts], [r.c13_2 for r in rts]
+    if all(x.shape == xs[0].shape and x.dtype == xs[0].dtype for x in xs) and \
+            all(h[0] for h in halves) and same(c31_1) and same(c13_1) and \
+            all(Fn.half_block_ok(x, c.spec.cin) for x, c in zip(xs, c31_1)):
+        # one launch for the first half-block (fused conv3x1 -> conv1x3, csrc/conv_hb.hip)
+        a2s = _half(xs, c31_1, c13_1, [r.bn1 for r in rts], [None] * len(xs))
+    else:
+        y1s = _convs(xs, c31_1, bias=bias(c31_1), act=ACT_RELU)
+        folds = [r.bn1.folded() for r in rts]
+        a2s = _convs(y1s, c13_1, bias=bias(c13_1), scale=[f[0] for f in folds],
+                     shift=[f[1] for f in folds], act=ACT_RELU)
+    if rts[0].cds is not None:
+        folds = [r.bnds.folded() for r in rts]
+        idns = _convs(xs, [r.cds for r in rts], scale=[f[0] for f in folds], shift=[f[1] for f in folds])
+    else:
+        idns = xs
+    if all(h[1] for h in halves) and same(c31_2) and same(c13_2) and \
+            all(a2.shape == a2s[0].shape for a2 in a2s) and \
+            all(Fn.half_block_ok(a2, c.spec.cin) for a2, c in zip(a2s, c31_2)) and \
+            all(Fn.ld_of(idn) == idn.shape[1] for idn in idns):
+        return _half(a2s, c31_2, c13_2, [r.bn2 for r in rts], idns)
+    y3s = _convs(a2s, c31_2, bias=bias(c31_2), act=ACT_RELU)
+    folds = [r.bn2.folded() for r in rts]
+    return _convs(y3s, c13_2, bias=bias(c13_2), scale=[f[0] for f in folds],
+                  shift=[f[1] for f in folds], residual=idns, act=ACT_RELU)
+
+
+def nbt1d_eval(x, rt):
+    """no-grad / eval fast path: both BatchNorms folded into the conv epilogues (4 launches; 2 where
+    the fused half-block kernel takes the map: small-batch 16-bit inference at C = 64 / 128)."""
+    return _nbt1d_eval([x], [rt])[0]
 
 
 def nbt1d_eval_pair(xa, xb, ra, rb):
     """nbt1d_eval of the SAME block of two twin networks (rgb | depth encoder, semantic | instance
-    decoder) in lockstep: every conv both blocks share a geometry for is one twin launch (4 instead
-    of 8 launches per block pair; at batch 1 a launch is its fixed cost).  Results == nbt1d_eval."""
-    b = lambda c: c.conv.bias.detach()   # noqa: E731
-    if (ra.cds is None) != (rb.cds is None):
-        raise _lib.EmsaError("twin NBt1D blocks differ in their skip path")
-    h1a, h2a = _half_block_specs(ra)
-    h1b, h2b = _half_block_specs(rb)
-    same1 = ra.c31_1.spec_key() == rb.c31_1.spec_key() and ra.c13_1.spec_key() == rb.c13_1.spec_key()
-    same2 = ra.c31_2.spec_key() == rb.c31_2.spec_key() and ra.c13_2.spec_key() == rb.c13_2.spec_key()
-    twin_ok = xa.shape == xb.shape and xa.dtype == xb.dtype
-    if twin_ok and h1a and h1b and same1 and Fn.half_block_ok(xa, ra.c31_1.spec.cin) and \
-            Fn.half_block_ok(xb, rb.c31_1.spec.cin):
-        # one launch for both twins' first half-block (fused conv3x1 -> conv1x3, csrc/conv_hb.hip)
-        a2a, a2b = _half([xa, xb], [ra.c31_1, rb.c31_1], [ra.c13_1, rb.c13_1], [ra.bn1, rb.bn1],
-                         [None, None])
-    else:
-        y1a, y1b = _conv_pair(xa, xb, ra.c31_1, rb.c31_1, bias=(b(ra.c31_1), b(rb.c31_1)), act=ACT_RELU)
-        (s1a, t1a), (s1b, t1b) = ra.bn1.folded(), rb.bn1.folded()
-        a2a, a2b = _conv_pair(y1a, y1b, ra.c13_1, rb.c13_1, bias=(b(ra.c13_1), b(rb.c13_1)),
-                              scale=(s1a, s1b), shift=(t1a, t1b), act=ACT_RELU)
-    if ra.cds is not None:
-        (sda, tda), (sdb, tdb) = ra.bnds.folded(), rb.bnds.folded()
-        ida, idb = _conv_pair(xa, xb, ra.cds, rb.cds, scale=(sda, sdb), shift=(tda, tdb))
-    else:
-        ida, idb = xa, xb
-    if h2a and h2b and same2 and a2a.shape == a2b.shape and Fn.half_block_ok(a2a, ra.c31_2.spec.cin) and \
-            Fn.half_block_ok(a2b, rb.c31_2.spec.cin) and Fn.ld_of(ida) == ida.shape[1] and \
-            Fn.ld_of(idb) == idb.shape[1]:
-        return _half([a2a, a2b], [ra.c31_2, rb.c31_2], [ra.c13_2, rb.c13_2], [ra.bn2, rb.bn2],
-                     [ida, idb])
-    y3a, y3b = _conv_pair(a2a, a2b, ra.c31_2, rb.c31_2, bias=(b(ra.c31_2), b(rb.c31_2)), act=ACT_RELU)
-    (s2a, t2a), (s2b, t2b) = ra.bn2.folded(), rb.bn2.folded()
-    return _conv_pair(y3a, y3b, ra.c13_2, rb.c13_2, bias=(b(ra.c13_2), b(rb.c13_2)),
-                      scale=(s2a, s2b), shift=(t2a, t2b), residual=(ida, idb), act=ACT_RELU)
+    decoder) in lockstep (4 instead of 8 launches per block pair; at batch 1 a launch is its fixed
+    cost).  Results == nbt1d_eval."""
+    return tuple(_nbt1d_eval([xa, xb], [ra, rb]))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1093,7 +1090,7 @@ class ConvBNActFunction(Function):
     @staticmethod
     def forward(ctx, x, crt, brt, act, weight, gamma, beta):
         x = Fn.as_act(x)
-        out, y, mean, invstd, mask = _conv_bn_forward(x, crt, brt, act)
+        out, y, mean, invstd, mask, _ = _conv_bn_forward(x, crt, brt, act)
         if act == ACT_RELU:
             _trace_mask('conv_bn_act', out)
         ctx.crt, ctx.brt, ctx.act = crt, brt, act
@@ -1112,7 +1109,7 @@ class ConvBNActFunction(Function):
         dout = Fn.as_act(dout, dense=True)
         dy, _, dg, db = Fn.bn_bwd(dout, mask, y, ctx.brt.bn.weight.detach(), mean, invstd, None,
                                   ctx.act, ctx.bn_train, want_dres=False, **_bn_targets(ctx.brt))
-        dx, dw, _ = _conv_backward(x, dy, ctx.crt, ctx.needs_input_grad[0])
+        dx, dw, _, _ = _conv_backward(x, dy, ctx.crt, ctx.needs_input_grad[0])
         return dx, None, None, None, dw, dg, db
 
 
@@ -1122,7 +1119,7 @@ class ConvBNAddActFunction(Function):
     @staticmethod
     def forward(ctx, x, residual, crt, brt, act, weight, gamma, beta):
         x, residual = Fn.as_act(x), Fn.as_act(residual, dense=True)
-        out, y, mean, invstd, mask = _conv_bn_forward(x, crt, brt, act, residual=residual)
+        out, y, mean, invstd, mask, _ = _conv_bn_forward(x, crt, brt, act, residual=residual)
         if act == ACT_RELU:
             _trace_mask('conv_bn_add_act', out)
         ctx.crt, ctx.brt, ctx.act = crt, brt, act
@@ -1142,7 +1139,7 @@ class ConvBNAddActFunction(Function):
         dy, dres, dg, db = Fn.bn_bwd(dout, mask, y, ctx.brt.bn.weight.detach(), mean, invstd, None,
                                      ctx.act, ctx.bn_train, want_dres=ctx.needs_input_grad[1],
                                      **_bn_targets(ctx.brt))
-        dx, dw, _ = _conv_backward(x, dy, ctx.crt, ctx.needs_input_grad[0])
+        dx, dw, _, _ = _conv_backward(x, dy, ctx.crt, ctx.needs_input_grad[0])
         return dx, dres, None, None, None, dw, dg, db
 
 
@@ -1669,7 +1666,7 @@ class SkipUpsampleFunction(Function):
         # recomputed from y, then the 1x1 conv's gradients
         dyk, dg, dbeta = Fn.bn_bwd_aff(dy, y, ctx.brt.bn.weight.detach(), mean, invstd,
                                        (scale, shift), **_bn_targets(ctx.brt))
-        dskip, dwc, _ = _conv_backward(skip, dyk, ctx.crt, ctx.needs_input_grad[1])
+        dskip, dwc, _, _ = _conv_backward(skip, dyk, ctx.crt, ctx.needs_input_grad[1])
         return (dx, dskip, None, None, dw.reshape(ctx.wshape), db if ctx.has_bias else None, dwc,
                 dg, dbeta)
 

@@ -10,8 +10,11 @@ import torch
 
 
 class _FakeLib:
+    generous = False      # True: every geometry query answers yes (see _GenerousLib)
+
     def __init__(self):
         self.calls = collections.Counter()
+        self.names = []   # entry points in call order
 
     def __getattr__(self, name):
         if not name.startswith('emsa_'):
@@ -19,6 +22,14 @@ class _FakeLib:
 
         def fn(*a):
             self.calls[name] += 1
+            self.names.append(name)
+            if self.generous:
+                if name.endswith('_supported'):
+                    return 1
+                if 'ws_bytes' in name:
+                    return 1024
+                if 'stats_rows' in name:
+                    return 3
             if name in ('emsa_conv_stats_rows', 'emsa_conv1d_wino_stats_rows', 'emsa_bn_bwd_rows'):
                 return 3
             if name in ('emsa_channel_ws_floats', 'emsa_bn_finalize_ws_bytes',
@@ -31,10 +42,15 @@ class _FakeLib:
         return fn
 
 
-@pytest.fixture
-def fake_lib(monkeypatch):
+class _GenerousLib(_FakeLib):
+    """the stub with every `*_supported` query answered 1, every `*ws_bytes*` query 1024 and every
+    `*stats_rows*` query 3: 16-bit training then gets past the stem, onto the register-stationary
+    convs and the multi-job weight gradient (the plain stub takes no 16-bit geometry)"""
+    generous = True
+
+
+def _install(monkeypatch, fake):
     from emsanet_amd import _lib, functional
-    fake = _FakeLib()
     monkeypatch.setattr(_lib, '_lib', fake)
     monkeypatch.setattr(functional, '_stream', lambda: 0)
     # like _bypass_device_check: the post-processing wrappers refuse host tensors, the dry run feeds
@@ -42,6 +58,16 @@ def fake_lib(monkeypatch):
     from emsanet_amd import postprocessing
     monkeypatch.setattr(postprocessing, '_dev', lambda t, name: t)
     return fake
+
+
+@pytest.fixture
+def fake_lib(monkeypatch):
+    return _install(monkeypatch, _FakeLib())
+
+
+@pytest.fixture
+def generous_lib(monkeypatch):
+    return _install(monkeypatch, _GenerousLib())
 
 
 def _model(args):
@@ -258,6 +284,58 @@ def test_dry_run_fused_bn_reduction(fake_lib, monkeypatch):
     assert c['emsa_bn_bwd_apply_rows_t'] == 50
     assert c['emsa_conv1d_wino_inbn'] == 0 and c['emsa_conv_wgrad_inbn'] == 0
     assert all(p.grad is not None for p in model.parameters())
+
+
+def test_dry_run_bf16_training_groups_block_weight_gradients(generous_lib, monkeypatch):
+    """bf16 training on the generous stub: every parameter gets a gradient of its own shape; the four
+    weight gradients of every NBt1D block are ONE multi-job launch, single launches are left to the
+    convs outside the blocks' four-conv chains (shortcuts, decoder and context convs, heads)"""
+    import emsanet_amd.model as M
+    from emsanet_amd import full_args
+    from emsanet_amd.nn import NonBottleneck1D
+    from oracle.emsanet_oracle import synthetic_batch
+    model = _model(full_args(input_height=64, input_width=96, compute_dtype='bfloat16')).train()
+    monkeypatch.setattr(M.EMSANet, 'forward', _bypass_device_check(model))
+    outs = model(synthetic_batch(2, 64, 96))
+    flat = [t for o, sides in outs for t in (list(o) if isinstance(o, tuple) else [o])]
+    flat += [t for _, sides in outs for s in sides for t in (list(s) if isinstance(s, tuple) else [s])]
+    torch.autograd.backward(flat, [torch.zeros_like(t) for t in flat])
+    for k, p in model.named_parameters():
+        assert p.grad is not None and p.grad.shape == p.shape, k
+    c = generous_lib.calls
+    blocks = sum(isinstance(m, NonBottleneck1D) for m in model.modules())
+    assert blocks == 50
+    assert c['emsa_conv_wgrad_multi_t'] == blocks
+    assert c['emsa_conv_wgrad_t'] == 45
+    assert c['emsa_conv1d_rs_t'] == 376
+
+
+def test_nbt1d_eval_pair_is_the_single_sequence_interleaved(fake_lib):
+    """fp32 host tensors (no twin launch exists): the launches of nbt1d_eval_pair are those of the
+    two nbt1d_eval calls, interleaved conv by conv; blocks that differ in their skip path are refused"""
+    from emsanet_amd import _lib, functional as Fn, ops
+    from emsanet_amd.nn import NonBottleneck1D
+
+    def launches(fn):
+        del fake_lib.names[:]
+        fn()
+        return list(fake_lib.names)
+    xa, xb = (Fn.as_act(torch.zeros(1, 64, 8, 12), dense=True) for _ in range(2))
+    for cout, stride, convs in ((64, 1, 4), (128, 2, 5)):
+        ra, rb = (NonBottleneck1D(64, cout, stride).eval()._rt for _ in range(2))
+        with torch.no_grad():
+            for x, r in ((xa, ra), (xb, rb)):       # (weights packed, BatchNorms folded: cached)
+                ops.nbt1d_eval(x, r)
+            ops.nbt1d_eval_pair(xa, xb, ra, rb)
+            a = launches(lambda: ops.nbt1d_eval(xa, ra))
+            b = launches(lambda: ops.nbt1d_eval(xb, rb))
+            pair = launches(lambda: ops.nbt1d_eval_pair(xa, xb, ra, rb))
+        assert len(a) == len(b) == convs
+        assert pair == [n for ab in zip(a, b) for n in ab]
+    plain, down = NonBottleneck1D(64, 64).eval()._rt, NonBottleneck1D(64, 64, 2).eval()._rt
+    with pytest.raises(_lib.EmsaError, match='skip path'), torch.no_grad():
+        ops.nbt1d_eval_pair(xa, xb, plain, down)
+    assert launches(lambda: None) == []
 
 
 def test_dry_run_fast_eval_uses_folded_kernels(fake_lib, monkeypatch):
