@@ -114,6 +114,10 @@ SIGNATURES = {
     'emsa_conv_wino2d_supported': (c_int, [_GP]),
     'emsa_conv_wino2d_stats_rows': (c_int, [_GP]),
     'emsa_conv_wino2d': (c_int, [_GP, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, _P, c_int32, c_int32, _P]),
+    'emsa_conv_wgrad_wino2d_supported': (c_int, [c_int32, _GP]),
+    'emsa_conv_wgrad_wino2d_ws_bytes': (c_int64, [c_int32, _GP]),
+    'emsa_conv_wgrad_wino2d_split_steps': (c_int, [c_int32, _GP]),
+    'emsa_conv_wgrad_wino2d': (c_int, [c_int32, _GP, _P, _P, _P, _P, _P, c_int32, _P]),
     'emsa_pack_wino2d': (c_int, [_P, _P, _P, c_int32, c_int32, _P]),
     'emsa_pack_wino2d_packed': (c_int, [_P, _P, c_int32, c_int32, c_int32, _P]),
     'emsa_pack_wino_packed': (c_int, [_P, _P, c_int32, c_int32, c_int32, c_int32, _P]),

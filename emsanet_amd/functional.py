@@ -1019,6 +1019,55 @@ def deterministic_wgrad():
     return os.environ.get('EMSA_DETERMINISTIC', '1') != '0'
 
 
+# The weight gradient of the dense 3x3 convs as 2-D Winograd F(3x3,2x2) (conv_wgrad_wino2d.hip)
+# instead of the row form F(3,2) with one kernel row per workgroup: read once from
+# EMSA_WGRAD_WINO2D (0 / 1 forces it off / on for every eligible shape).
+_WGRAD_WINO2D_ENV = os.environ.get('EMSA_WGRAD_WINO2D')
+WGRAD_WINO2D = None          # tests: True / False overrides the per-shape rule
+_BF16_MFMA = os.environ.get('EMSA_BF16_MFMA', '0')[:1] == '1'   # read once, as the library does
+# per-shape rule (cin, cout) -> 2-D form, from profiles/wgrad2d_conv_bench.txt: the shapes it
+# measured faster on than the row kernel (reduction launch included on both sides)
+WGRAD_WINO2D_SHAPES = frozenset({(512, 512), (512, 256), (256, 128), (128, 40), (128, 96), (96, 8)})
+# selected convs that ran on the row kernel all the same (the library refused the geometry)
+WGRAD_WINO2D_FALLBACKS = 0
+
+
+def wgrad_wino2d_selected(spec):
+    """the weight gradient of this 3x3 conv runs the 2-D Winograd kernel (fp32 activations)"""
+    if not wino2d_eligible(spec) or _BF16_MFMA:
+        return False              # (the opt-in bf16-MFMA mode is a form of the row kernel only)
+    if WGRAD_WINO2D is not None:
+        return bool(WGRAD_WINO2D)
+    if _WGRAD_WINO2D_ENV is not None:
+        return _WGRAD_WINO2D_ENV != '0'
+    return (spec.cin, spec.cout) in WGRAD_WINO2D_SHAPES
+
+
+def _conv_wgrad_wino2d(x, dy, spec, g, want_bias, like, dw_out, db_out):
+    """-> (dw, db, packed) of conv_wgrad, or None: the library refuses this geometry"""
+    global WGRAD_WINO2D_FALLBACKS
+    L = _lib.lib()
+    ws_bytes = L.emsa_conv_wgrad_wino2d_ws_bytes(0, g) if L.emsa_conv_wgrad_wino2d_supported(0, g) else 0
+    if ws_bytes <= 0:
+        WGRAD_WINO2D_FALLBACKS += 1
+        return None
+    nw = 9 * spec.cout * spec.cin
+    ws = _empty((ws_bytes // 4,), x.device)
+    if like is not None and dw_out is not None and (db_out is not None or not want_bias):
+        dw, db = dw_out.view(-1), db_out
+    else:
+        buf = _empty((nw + (spec.cout if want_bias else 0),), x.device)
+        dw = buf[:nw]
+        db = buf[nw:] if want_bias else None
+    # like = the weight: straight into the parameter layout; without it the packed form
+    packed = like is None
+    check(L.emsa_conv_wgrad_wino2d(0, g, _p(x), _p(dy), _p(dw), _p(db), _p(ws), 1 if packed else 0,
+                                   _stream()), 'emsa_conv_wgrad_wino2d')
+    if packed:
+        return dw, db, True
+    return dw.view(like.shape), db, False
+
+
 def conv_wgrad(x, dy, spec, want_bias, like=None, two_pass=None, dw_out=None, db_out=None,
                in_affine=None):
     """weight (+bias) gradient.  returns (dw, dbias or None, packed):
@@ -1033,6 +1082,11 @@ def conv_wgrad(x, dy, spec, want_bias, like=None, two_pass=None, dw_out=None, db
         two_pass = deterministic_wgrad()
     n, c, h, w = x.shape
     g = spec.geom_fwd(n, h, w, ld_of(x), ld_of(dy))
+    if (in_affine is None and x.dtype == torch.float32 and dy.dtype == torch.float32 and
+            two_pass is not False and wgrad_wino2d_selected(spec)):
+        res = _conv_wgrad_wino2d(x, dy, spec, g, want_bias, like, dw_out, db_out)
+        if res is not None:
+            return res
     L = _lib.lib()
     taps = spec.kh * spec.kw
     nw = taps * spec.cout * spec.cin

@@ -207,6 +207,23 @@ int emsa_conv_wino2d(const EmsaConvGeom* g, const float* in, const float* u2, fl
                      const float* bias, float* stats, const float* scale, const float* shift,
                      const float* residual, int32_t ld_res, const float* mask_src,
                      int32_t ld_mask, int32_t act, void* stream);
+/* 2-D Winograd F(3x3,2x2) weight gradient of the same convolutions (conv_wgrad_wino2d.hip): the
+ * transpose of emsa_conv_wino2d, 16 GEMMs over the 2x2 tiles of dy where the row form of
+ * emsa_conv_wgrad runs 24 of the 36 direct multiplies and stages both operands three times.
+ * g = the conv's FORWARD geometry as for emsa_conv_wgrad; dtype = storage type of in / dout
+ * (EMSA_DT_F32 only).  Always the deterministic two-pass form: ws of at least
+ * emsa_conv_wgrad_wino2d_ws_bytes(dtype, g) bytes receives the split-K partial tiles and one
+ * reduction launch writes dw -- packed = 0: the OIHW parameter layout [n][c][3][3]; packed = 1:
+ * [tap][n][c] (what emsa_unpack_wgrad reads) -- and dbias (may be NULL).  No atomics, nothing to
+ * zero, bit-reproducible.  in, dout, dw and ws 16-byte aligned.  EMSA_E_SHAPE before any launch
+ * for whatever emsa_conv_wgrad_wino2d_supported refuses: 16-bit storage, stride, dilation, 1-D
+ * kernels, a mapped geometry, channel counts or strides that are no multiple of 4, tensors of
+ * 2 GiB or more.  emsa_conv_wgrad_wino2d_split_steps: K steps (of 8 tiles) per split of the plan. */
+int emsa_conv_wgrad_wino2d_supported(int32_t dtype, const EmsaConvGeom* g);
+int64_t emsa_conv_wgrad_wino2d_ws_bytes(int32_t dtype, const EmsaConvGeom* g);
+int emsa_conv_wgrad_wino2d_split_steps(int32_t dtype, const EmsaConvGeom* g);
+int emsa_conv_wgrad_wino2d(int32_t dtype, const EmsaConvGeom* g, const void* in, const void* dout,
+                           float* dw, float* dbias, float* ws, int32_t packed, void* stream);
 int emsa_pack_wino2d(const float* w_oihw, float* u, float* u_dgrad, int32_t cout, int32_t cin,
                      void* stream);
 int emsa_pack_wino2d_packed(const float* w_packed, float* u, int32_t n_ch, int32_t k_ch,

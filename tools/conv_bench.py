@@ -1,6 +1,8 @@
 """Micro-benchmark of the MFMA convolution kernels on the layer shapes of the bs=32 640x480
-workload (GPU box).  usage: python tools/conv_bench.py [fwd|dgrad|wgrad|wino|wino2d|all] [tile ...]
-(wino2d: the dense 3x3 convs, row-Winograd versus 2-D F(2x2,3x3) in the same run)
+workload (GPU box).  usage: python tools/conv_bench.py [fwd|dgrad|wgrad|wino|wino2d|wgrad2d|all] [tile ...]
+(wino2d: the dense 3x3 convs, row-Winograd versus 2-D F(2x2,3x3) in the same run;
+ wgrad2d: their weight gradient, row form F(3,2) versus 2-D F(3x3,2x2), reduction launch included
+ on both sides, median / min / max of 20 device-event timings per side)
 EMSA_LIB selects an alternative build (ablations)."""
 import os
 import sys
@@ -24,6 +26,7 @@ SHAPES = [
     ('3x3 256->128 /8', 256, 128, (3, 3), 1, (1, 1), 60, 80),
     ('3x3 128->40 /4', 128, 40, (3, 3), 1, (1, 1), 120, 160),
     ('3x3 128->96 /4', 128, 96, (3, 3), 1, (1, 1), 120, 160),
+    ('3x3 96->8 /4', 96, 8, (3, 3), 1, (1, 1), 120, 160),
     # memory-bound 1x1 convs (decoder skip connections) and a stride-2 block conv
     ('1x1 c64 /4', 64, 64, (1, 1), 1, (0, 0), 120, 160),
     ('1x1 c128 /8', 128, 128, (1, 1), 1, (0, 0), 60, 80),
@@ -47,6 +50,22 @@ def timeit(fn, iters=24):
     return a.elapsed_time(b) / iters * 1e3     # us
 
 
+def time_each(fn, iters=20):
+    """one device-event pair per call of fn(i) -> (median, min, max) in us"""
+    for i in range(3):
+        fn(i)
+    torch.cuda.synchronize()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+          for _ in range(iters)]
+    for i, (a, b) in enumerate(ev):
+        a.record()
+        fn(i)
+        b.record()
+    torch.cuda.synchronize()
+    t = sorted(a.elapsed_time(b) * 1e3 for a, b in ev)
+    return t[len(t) // 2], t[0], t[-1]
+
+
 def main():
     what = sys.argv[1] if len(sys.argv) > 1 else 'all'
     tiles = [int(t) for t in sys.argv[2:]] or [-1]
@@ -57,7 +76,7 @@ def main():
         if only and only not in name:
             continue
         spec = Fn.ConvSpec(cin, cout, k, s, p)
-        if what == 'wino2d' and not Fn.wino2d_eligible(spec):
+        if what in ('wino2d', 'wgrad2d') and not Fn.wino2d_eligible(spec):
             continue
         oh, ow = spec.out_hw(h, w)
         set_bytes = 4 * n * (2 * cin * h * w + 2 * cout * oh * ow)
@@ -136,6 +155,16 @@ def main():
             pw = timeit(lambda i: Fn.bn_act(X[i % nb], aff[0], aff[1], None, None, 1,
                                             want_mask=True))
             row += f" (bn_act pass {pw:6.1f}us)"
+        if what == 'wgrad2d':
+            res = {}
+            for tag, on in (('row', False), ('2d', True)):
+                Fn.WGRAD_WINO2D = on
+                res[tag] = time_each(lambda i: Fn.conv_wgrad(X[i % nb], DY[i % nb], spec, True, like=wt,
+                                                             two_pass=True))
+                row += f" {tag} {res[tag][0]:7.1f}us ({res[tag][1]:.1f}..{res[tag][2]:.1f}) |"
+            Fn.WGRAD_WINO2D = None
+            row += (f" x{res['row'][0] / res['2d'][0]:4.2f} | 2d {flops / res['2d'][0] / 1e6:6.1f}TF(algo)"
+                    f" fallbacks {Fn.WGRAD_WINO2D_FALLBACKS}")
         if what in ('wgrad', 'all'):
             us = timeit(lambda i: Fn.conv_wgrad(X[i % nb], DY[i % nb], spec, True))
             row += f" wgrad {us:7.1f}us {flops / us / 1e6:6.1f}TF |"
