@@ -71,6 +71,43 @@ def _traced(fn):
 # ---------------------------------------------------------------------------------------------
 # runtime views of parameter containers
 # ---------------------------------------------------------------------------------------------
+class _PackCache:
+    """The packed forms of one conv's weights: (form, dtype) -> [key_fwd, fwd, key_dgrad, dgrad].  A
+    side is valid while its key equals the conv's current one (the parameters' versions and
+    addresses); the owner packs into it on a miss (`get`), PackPlan installs its views (`put`)."""
+
+    def __init__(self):
+        self._slots = {}
+
+    def get(self, form, dtype, side, key, pack, both):
+        """side 0: forward operand, 1: data-gradient operand.  A forward miss calls
+        pack(fwd=True, dgrad=both) -- `both`: the data gradient will be wanted too, one launch for
+        the two -- a data-gradient miss pack(fwd=False, dgrad=True); pack returns (fwd, dgrad)"""
+        ent = self._slots.get((form, dtype))
+        if ent is None:
+            ent = self._slots[(form, dtype)] = [None, None, None, None]
+        if ent[2 * side] != key:
+            if side == 0:
+                ent[1], d = pack(fwd=True, dgrad=both)
+                ent[0] = key
+                if d is not None:
+                    ent[2], ent[3] = key, d
+            else:
+                ent[3] = pack(fwd=False, dgrad=True)[1]
+                ent[2] = key
+        return ent[2 * side + 1]
+
+    def put(self, form, dtype, key, fwd, dgrad):
+        """overwrites the whole slot: an older data-gradient operand is dropped, never kept beside a
+        newer forward one (it would pin the arena it is a view of)"""
+        self._slots[(form, dtype)] = [key, fwd, key if dgrad is not None else None, dgrad]
+
+    def peek(self, form, dtype, key):
+        """(fwd, dgrad) as stored under `key`, None for a side that is absent or stale; never packs"""
+        ent = self._slots.get((form, dtype), (None, None, None, None))
+        return ent[1] if ent[0] == key else None, ent[3] if ent[2] == key else None
+
+
 class ConvRT:
     """nn.Conv2d used as a parameter container + cached packed weights.  fp32 activations run on
     the fp32 kernels (Winograd where eligible); 16-bit activations on conv_h.hip with the weights
@@ -80,47 +117,48 @@ class ConvRT:
         self.conv = conv
         self.spec = Fn.ConvSpec(conv.in_channels, conv.out_channels, tuple(conv.kernel_size),
                                 tuple(conv.stride), tuple(conv.padding))
-        self._key = None
-        self._wp = None
-        self._keyd = None
-        self._wpd = None
         # stride-1 3x1 / 1x3 convs run on the Winograd F(2,3) kernel (EMSA_WINO=0 disables it)
         self.wino = Fn.wino_eligible(self.spec) and os.environ.get('EMSA_WINO', '1') != '0'
-        self._keyu = None
-        self._u = None
-        self._ud = None
         # dense 3x3 convs the per-shape rule sends to the 2-D Winograd F(2x2,3x3) kernel hold its
         # weights U2 as well; the row form stays (fallback for what that kernel refuses)
         self.wino2d = self.wino and Fn.wino2d_selected(self.spec)
-        self._keyu2 = None
-        self._u2 = None
-        self._ud2 = None
-        self._h = {}              # 16-bit packs: dtype -> [key, fwd, key_d, dgrad]
         # stride-1 3x1 / 1x3 convs with 64..512 channels in 16-bit storage: the register-stationary
         # streaming kernel (conv_rs.hip) with fragment-ordered weights, where it takes the geometry
         self.rs = Fn.rs_eligible(self.spec)
-        self._hf = {}             # fragment-ordered 16-bit packs: dtype -> [key, fwd, key_d, dgrad]
+        # forms: 'gemm' [tap][n][k] (fp32 and 16-bit), 'wino' U, 'wino2d' U2 (fp32), 'frag'
+        # fragment-ordered (16-bit)
+        self.packs = _PackCache()
         self.plain_asked = 0      # times the [tap][n][k] 16-bit operand of an rs conv was read (PackPlan)
 
     def spec_key(self):
         s = self.spec
         return (s.cin, s.cout, s.kh, s.kw, s.sh, s.sw, s.ph, s.pw)
 
-    def _wino_weights(self):
+    def key_now(self):
         w = self.conv.weight
-        key = (w._version, w.data_ptr())
-        if key != self._keyu:
-            self._u, self._ud = Fn.pack_wino(w.detach(), fwd=True, dgrad=w.requires_grad)
-            self._keyu = key
-        return self._u, self._ud
+        return (w._version, w.data_ptr())
 
-    def _wino2d_weights(self):
-        w = self.conv.weight
-        key = (w._version, w.data_ptr())
-        if key != self._keyu2:
-            self._u2, self._ud2 = Fn.pack_wino2d(w.detach(), fwd=True, dgrad=w.requires_grad)
-            self._keyu2 = key
-        return self._u2, self._ud2
+    def _pack(self, form, dtype, fwd, dgrad):
+        w = self.conv.weight.detach()
+        if form == 'wino':
+            return Fn.pack_wino(w, fwd=fwd, dgrad=dgrad)
+        if form == 'wino2d':
+            return Fn.pack_wino2d(w, fwd=fwd, dgrad=dgrad)
+        if form == 'frag':
+            return Fn.pack_weight_frag_t(w, dtype, fwd=fwd, dgrad=dgrad)
+        if dtype != torch.float32:
+            return Fn.pack_weight_t(w, dtype, fwd=fwd, dgrad=dgrad)
+        if fwd and dgrad:
+            # trainable: the data-gradient layout will be needed too -> one launch for both
+            return Fn.pack_weight_pair(w)
+        return (Fn.pack_weight(w, 'fwd'), None) if fwd else (None, Fn.pack_weight(w, 'dgrad'))
+
+    def weights(self, form, side, dtype=torch.float32):
+        """the forward (side 0) / data-gradient (side 1) operand of `form`: PackPlan's when fresh,
+        else packed here -- both sides at a forward miss of a trainable weight"""
+        w = self.conv.weight           # (one module attribute lookup per call: this is the hot path)
+        return self.packs.get(form, dtype, side, (w._version, w.data_ptr()),
+                              lambda fwd, dgrad: self._pack(form, dtype, fwd, dgrad), w.requires_grad)
 
     def forward(self, x, **kw):
         """conv forward through the best kernel for this layer (fused-epilogue kwargs of conv_fwd)"""
@@ -128,10 +166,10 @@ class ConvRT:
             wf = self.frag(x.dtype)
             return Fn.conv_fwd(x, self._plain(x.dtype, wf, self.packed), self.spec, wfrag=wf, **kw)
         if self.wino2d:
-            return Fn.conv_fwd(x, None, self.spec, wino2d_u=self._wino2d_weights()[0],
-                               wino_u=lambda: self._wino_weights()[0], **kw)
+            return Fn.conv_fwd(x, None, self.spec, wino2d_u=self.weights('wino2d', 0),
+                               wino_u=lambda: self.weights('wino', 0), **kw)
         if self.wino:
-            return Fn.conv_fwd(x, None, self.spec, wino_u=self._wino_weights()[0], **kw)
+            return Fn.conv_fwd(x, None, self.spec, wino_u=self.weights('wino', 0), **kw)
         return Fn.conv_fwd(x, self.packed(), self.spec, **kw)
 
     def folds_input_bn(self, t):
@@ -150,13 +188,10 @@ class ConvRT:
             return Fn.conv_dgrad(dy, self._plain(dy.dtype, wf, self.packed_dgrad), self.spec, in_hw,
                                  wfrag=wf, **kw)
         if self.wino2d and mask_bits is None:
-            ud2 = self._wino2d_weights()[1]
-            if ud2 is None:
-                ud2 = Fn.pack_wino2d(self.conv.weight.detach(), fwd=False, dgrad=True)[1]
-            return Fn.conv_dgrad(dy, None, self.spec, in_hw, wino2d_u=ud2,
-                                 wino_u=self._row_dgrad_weights, **kw)
+            return Fn.conv_dgrad(dy, None, self.spec, in_hw, wino2d_u=self.weights('wino2d', 1),
+                                 wino_u=lambda: self.weights('wino', 1), **kw)
         if self.wino:
-            return Fn.conv_dgrad(dy, None, self.spec, in_hw, wino_u=self._row_dgrad_weights(),
+            return Fn.conv_dgrad(dy, None, self.spec, in_hw, wino_u=self.weights('wino', 1),
                                  mask_bits=mask_bits, **kw)
         return Fn.conv_dgrad(dy, self.packed_dgrad(), self.spec, in_hw, **kw)
 
@@ -164,12 +199,6 @@ class ConvRT:
         """this conv's data gradient can mask its residual operand by bits (Fn.conv_dgrad res_bits):
         the fp32 1-D Winograd launch, whole 64-channel tiles"""
         return self.wino and not self.wino2d and Fn.dgrad_takes_res_bits(self.spec, dy, in_hw, residual)
-
-    def _row_dgrad_weights(self):
-        ud = self._wino_weights()[1]
-        if ud is None:
-            ud = Fn.pack_wino(self.conv.weight.detach(), fwd=False, dgrad=True)[1]
-        return ud
 
     def dgrad_bnb(self, dy, in_hw, t, affine, mean, invstd, residual=None, force=False):
         """data gradient + the backward reduction of the BatchNorm in front of this conv
@@ -185,11 +214,8 @@ class ConvRT:
                                      t, scale, shift, mean, invstd, residual=residual, wfrag=wf)
         if not self.wino:
             return None
-        u, ud = self._wino_weights()
-        if ud is None:
-            ud = Fn.pack_wino(self.conv.weight.detach(), fwd=False, dgrad=True)[1]
         return Fn.conv_dgrad_bnb(dy, None, self.spec, in_hw, t, scale, shift, mean, invstd,
-                                 residual=residual, wino_u=ud)
+                                 residual=residual, wino_u=self.weights('wino', 1))
 
     def _plain(self, dtype, wfrag, getter):
         """the [tap][n][k] operand of the implicit GEMM: at once for a conv without fragment-ordered
@@ -201,67 +227,20 @@ class ConvRT:
 
         return lambda: getter(dtype)
 
-    def frag(self, dtype):
-        """fragment-ordered forward weights for conv_rs.hip (None: not that kind of conv)"""
-        if not (self.rs and Fn.CONV_RS):
-            return None
-        w = self.conv.weight
-        key = (w._version, w.data_ptr())
-        ent = self._hf.setdefault(dtype, [None, None, None, None])
-        if ent[0] != key:
-            ent[1], d = Fn.pack_weight_frag_t(w.detach(), dtype, fwd=True, dgrad=w.requires_grad)
-            ent[0] = key
-            if d is not None:
-                ent[2], ent[3] = key, d
-        return ent[1]
+    def frag(self, dtype, side=0):
+        """fragment-ordered weights for conv_rs.hip (None: not that kind of conv)"""
+        return self.weights('frag', side, dtype) if self.rs and Fn.CONV_RS else None
 
     def frag_dgrad(self, dtype):
-        if not (self.rs and Fn.CONV_RS):
-            return None
-        w = self.conv.weight
-        key = (w._version, w.data_ptr())
-        ent = self._hf.setdefault(dtype, [None, None, None, None])
-        if ent[2] != key:
-            ent[3] = Fn.pack_weight_frag_t(w.detach(), dtype, fwd=False, dgrad=True)[1]
-            ent[2] = key
-        return ent[3]
+        return self.frag(dtype, 1)
 
-    def packed(self, dtype=torch.float32):
-        w = self.conv.weight
-        key = (w._version, w.data_ptr())
+    def packed(self, dtype=torch.float32, side=0):
         if dtype != torch.float32:
             self.plain_asked += 1
-            ent = self._h.setdefault(dtype, [None, None, None, None])
-            if ent[0] != key:
-                ent[1], d = Fn.pack_weight_t(w.detach(), dtype, fwd=True, dgrad=w.requires_grad)
-                ent[0] = key
-                if d is not None:
-                    ent[2], ent[3] = key, d
-            return ent[1]
-        if key != self._key:
-            if w.requires_grad:
-                # trainable: the data-gradient layout will be needed too -> one launch for both
-                self._wp, self._wpd = Fn.pack_weight_pair(w.detach())
-                self._keyd = key
-            else:
-                self._wp = Fn.pack_weight(w.detach(), 'fwd')
-            self._key = key
-        return self._wp
+        return self.weights('gemm', side, dtype)
 
     def packed_dgrad(self, dtype=torch.float32):
-        w = self.conv.weight
-        key = (w._version, w.data_ptr())
-        if dtype != torch.float32:
-            self.plain_asked += 1
-            ent = self._h.setdefault(dtype, [None, None, None, None])
-            if ent[2] != key:
-                ent[3] = Fn.pack_weight_t(w.detach(), dtype, fwd=False, dgrad=True)[1]
-                ent[2] = key
-            return ent[3]
-        if key != self._keyd:
-            self._wpd = Fn.pack_weight(w.detach(), 'dgrad')
-            self._keyd = key
-        return self._wpd
+        return self.packed(dtype, 1)
 
 
 # EMSA_PACK_LEAN=0: always pack both 16-bit operand forms of the conv_rs-capable convs (A/B runs)
@@ -273,8 +252,8 @@ class PackPlan:
     operands of the mixed-precision path) in ONE launch per optimizer step instead of one ~5 us
     kernel per layer (380 launches = 2.3 ms per step).  `refresh(dtype)` (called at the start of
     the model's forward) re-packs every registered ConvRT when any weight changed and installs the
-    results as the ConvRTs' own caches, so their per-layer fallbacks (`packed()`,
-    `_wino_weights()`) find fresh entries and launch nothing."""
+    results in the ConvRTs' own caches (`_PackCache.put`), so their per-layer fallback
+    (`weights()`) finds fresh entries and launches nothing."""
 
     def __init__(self, rts):
         self.rts = [rt for rt in rts if isinstance(rt, ConvRT)]
@@ -455,7 +434,7 @@ class PackPlan:
         if not self.rts:
             return
         ws = [rt.conv.weight for rt in self.rts]
-        mkeys = [m._key_now() for m in self.multi]
+        mkeys = [m.key_now() for m in self.multi]
         key = (dtype,) + tuple((w._version, w.data_ptr(), w.requires_grad) for w in ws) + \
             tuple(mkeys)
         if key == self._key:
@@ -482,36 +461,20 @@ class PackPlan:
         check(_lib.lib().emsa_pack_batch(self._jobs.data_ptr(), self._n_jobs, self._n_blocks,
                                          Fn._stream()), 'emsa_pack_batch')
         for m, mk, (d0, d1, bias, wino, d2, d3) in zip(self.multi, mkeys, self._mviews):
+            # (an fp32 Winograd head gets U and the bias, no GEMM operand)
+            m.packs.put('wino' if wino else 'gemm', dtype, mk, d0, d1)
+            m.packs.put('bias', torch.float32, mk, bias, None)
             if d2 is not None:
-                m._u2, m._ud2, m._key2 = d2, d3, mk
-            if dtype != torch.float32:
-                m._h[dtype] = (mk, d0, bias)
-                m._hd[dtype] = (mk, d1, None)
-            elif wino:
-                m._wp, m._bias, m._u, m._key = None, bias, d0, mk
-                m._hd[dtype] = (mk, None, d1)
-            else:
-                m._wp, m._bias, m._u, m._key = d0, bias, None, mk
-                m._hd[dtype] = (mk, d1, None)
+                m.packs.put('wino2d', dtype, mk, d2, d3)
         for rt, (f0, f1) in zip(*self._frag):
-            w = rt.conv.weight
-            k = (w._version, w.data_ptr())
-            rt._hf[dtype] = [k, f0, k if f1 is not None else None, f1]
+            rt.packs.put('frag', dtype, rt.key_now(), f0, f1)
         for rt, (u0, u1) in zip(*self._w2):
-            w = rt.conv.weight
-            rt._u2, rt._ud2, rt._keyu2 = u0, u1, (w._version, w.data_ptr())
-        for rt, (v0, v1), w in zip(self.rts, self._views, ws):
-            k = (w._version, w.data_ptr())
+            rt.packs.put('wino2d', dtype, rt.key_now(), u0, u1)
+        for rt, (v0, v1) in zip(self.rts, self._views):
             if v0 is None:
                 continue                       # lean: ConvRT.packed packs this one itself if asked
-            if dtype != torch.float32:
-                rt._h[dtype] = [k, v0, k if v1 is not None else None, v1]
-            elif rt.wino:
-                rt._u, rt._ud, rt._keyu = v0, v1, k
-            else:
-                rt._wp, rt._key = v0, k
-                if v1 is not None:
-                    rt._wpd, rt._keyd = v1, k
+            rt.packs.put('wino' if rt.wino and dtype == torch.float32 else 'gemm', dtype,
+                         rt.key_now(), v0, v1)
         self._key = key
 
 
@@ -1158,123 +1121,47 @@ class MultiConvRT:
     def __init__(self, placements, cout_total, cin_total, kernel, padding):
         self.placements = placements
         self.spec = Fn.ConvSpec(cin_total, cout_total, kernel, 1, padding)
-        self._key = None
-        self._wp = None
-        self._bias = None
-        self._u = None
-        self._h = {}                 # 16-bit packs: dtype -> (key, wp, bias)
-        self._hd = {}                # data-gradient packs: dtype -> (key, wpd, Winograd U or None)
         self.has_bias = any(m.bias is not None for m, _, _ in placements)
         # 3x3 stride-1 merged convs (the task heads) run on the Winograd kernel as well
         self.wino = Fn.wino_eligible(self.spec) and os.environ.get('EMSA_WINO', '1') != '0'
         # merged 3x3 heads the per-shape rule sends to the 2-D Winograd kernel: U2 beside the row form
         self.wino2d = self.wino and Fn.wino2d_selected(self.spec)
-        self._key2 = None
-        self._u2 = None              # forward U2
-        self._ud2 = None             # data-gradient U2 (same key)
-
-    def _wino2d_weights(self):
-        """(forward, data-gradient) U2 of the assembled operand: PackPlan's when fresh, else re-packed"""
-        key = self._key_now()
-        if key != self._key2:
-            s = self.spec
-            self._u2 = Fn.pack_wino2d_packed(self._packed_fwd(),
-                                             s.cout, s.cin, flip=False)
-            self._ud2 = Fn.pack_wino2d_packed(self.packed_dgrad(), s.cin, s.cout, flip=True)
-            self._key2 = key
-        return self._u2, self._ud2
-
-    def _packed_fwd(self):
-        s = self.spec
-        wp = Fn._zeros((s.kh * s.kw * s.cout * s.cin,), self.placements[0][0].weight.device)
-        for m, co, ci in self.placements:
-            Fn.pack_weight(self._w4(m).detach(), 'fwd', s.cout, co, s.cin, ci, out=wp)
-        return wp
+        # forms: 'gemm' the assembled [tap][n][k] operands (fp32 and 16-bit), 'wino' U and 'wino2d'
+        # U2 made from them (fp32), 'bias' the assembled fp32 bias vector (forward side only)
+        self.packs = _PackCache()
 
     def _w4(self, m):
         w = m.weight
         return w if w.dim() == 4 else w[:, :, None, None]
 
-    def _key_now(self):
+    def key_now(self):
         return tuple((m.weight._version, m.weight.data_ptr(),
                       m.bias._version if m.bias is not None else 0) for m, _, _ in self.placements)
 
-    def _bias_vec(self, dev):
-        bias = torch.zeros(self.spec.cout, device=dev, dtype=torch.float32)
+    def _bias_vec(self):
+        bias = torch.zeros(self.spec.cout, device=self.placements[0][0].weight.device,
+                           dtype=torch.float32)
         for m, co, _ in self.placements:
             if m.bias is not None:
                 bias[co:co + m.bias.shape[0]].copy_(m.bias.detach())
         return bias
 
-    def packed(self):
-        key = self._key_now()
-        if key != self._key:
-            s = self.spec
-            wp = Fn._zeros((s.kh * s.kw * s.cout * s.cin,), self.placements[0][0].weight.device)
-            for m, co, ci in self.placements:
+    # the assembled operands start as zeros: the padding channels and whatever lies between the
+    # placements belong to no parameter, and the kernels read them like any other weight
+    def _assemble_fwd(self, dtype):
+        """forward operand [tap][cout][cin], fp32 or 16-bit"""
+        s = self.spec
+        wp = Fn._zeros((s.kh * s.kw * s.cout * s.cin,), self.placements[0][0].weight.device, dtype)
+        for m, co, ci in self.placements:
+            if dtype == torch.float32:
                 Fn.pack_weight(self._w4(m).detach(), 'fwd', s.cout, co, s.cin, ci, out=wp)
-            bias = self._bias_vec(wp.device) if self.has_bias else None
-            self._wp, self._bias, self._key = wp, bias, key
-            self._u = Fn.pack_wino_packed(wp, s.cout, s.cin, Fn.wino_rows(s), flip=False) \
-                if self.wino else None
-        return self._wp, self._bias
-
-    def packed_t(self, dtype):
-        """16-bit forward operand [tap][cout][cin] (+ fp32 bias vector)"""
-        key = self._key_now()
-        ent = self._h.get(dtype)
-        if ent is None or ent[0] != key:
-            s = self.spec
-            dev = self.placements[0][0].weight.device
-            wp = Fn._zeros((s.kh * s.kw * s.cout * s.cin,), dev, dtype)
-            for m, co, ci in self.placements:
+            else:
                 Fn.pack_weight_t(self._w4(m).detach(), dtype, True, False, s.cout, co, s.cin, ci,
                                  out_fwd=wp)
-            ent = (key, wp, self._bias_vec(dev) if self.has_bias else None)
-            self._h[dtype] = ent
-        return ent[1], ent[2]
+        return wp
 
-    def forward(self, x):
-        Fn.prof_flops(self.real_flops(x))
-        if x.dtype != torch.float32:
-            wp, bias = self.packed_t(x.dtype)
-            return Fn.conv_fwd(x, wp, self.spec, bias=bias)
-        wp, bias = self.packed()
-        if self.wino2d:
-            return Fn.conv_fwd(x, None, self.spec, bias=bias, wino_u=self._u,
-                               wino2d_u=self._wino2d_weights()[0])
-        if self.wino:
-            return Fn.conv_fwd(x, None, self.spec, bias=bias, wino_u=self._u)
-        return Fn.conv_fwd(x, wp, self.spec, bias=bias)
-
-    def real_flops(self, x):
-        """direct-convolution FLOPs of the REAL (un-padded, un-merged) convolutions on `x`"""
-        n, _, h, w = x.shape
-        return 2.0 * n * h * w * sum(m.weight.numel() for m, _, _ in self.placements)
-
-    def dgrad(self, dy, in_hw):
-        Fn.prof_flops(self.real_flops(dy))
-        # the data-gradient operands are rebuilt only when a parameter moved (they used to be
-        # re-packed at every call: a zero-fill and 2-4 small kernels per head and step)
-        key = self._key_now()
-        ent = self._hd.get(dy.dtype)
-        if ent is None or ent[0] != key:
-            wpd = self.packed_dgrad(dy.dtype)
-            ud = None
-            if self.wino and dy.dtype == torch.float32:
-                s = self.spec
-                ud = Fn.pack_wino_packed(wpd, s.cin, s.cout, Fn.wino_rows(s), flip=True)
-            ent = (key, wpd, ud)
-            self._hd[dy.dtype] = ent
-        _, wpd, ud = ent
-        if ud is not None and self.wino2d:
-            return Fn.conv_dgrad(dy, None, self.spec, in_hw, wino_u=ud,
-                                 wino2d_u=self._wino2d_weights()[1])
-        if ud is not None:
-            return Fn.conv_dgrad(dy, None, self.spec, in_hw, wino_u=ud)
-        return Fn.conv_dgrad(dy, wpd, self.spec, in_hw)
-
-    def packed_dgrad(self, dtype=torch.float32):
+    def _assemble_dgrad(self, dtype):
+        """data-gradient operand [tap][cin][cout], fp32 or 16-bit"""
         s = self.spec
         wp = Fn._zeros((s.kh * s.kw * s.cout * s.cin,), self.placements[0][0].weight.device, dtype)
         for m, co, ci in self.placements:
@@ -1284,6 +1171,56 @@ class MultiConvRT:
                 Fn.pack_weight_t(self._w4(m).detach(), dtype, False, True, s.cout, co, s.cin, ci,
                                  out_dgrad=wp)
         return wp
+
+    def _pack(self, form, dtype, fwd, dgrad):
+        s = self.spec
+        if form == 'bias':
+            return self._bias_vec(), None
+        if form == 'gemm':
+            return (self._assemble_fwd(dtype) if fwd else None,
+                    self._assemble_dgrad(dtype) if dgrad else None)
+        # U / U2 from the CACHED assembled operands: one assembly serves both
+        if form == 'wino':
+            rows = Fn.wino_rows(s)
+            return (Fn.pack_wino_packed(self.weights('gemm', 0), s.cout, s.cin, rows, flip=False)
+                    if fwd else None,
+                    Fn.pack_wino_packed(self.weights('gemm', 1), s.cin, s.cout, rows, flip=True)
+                    if dgrad else None)
+        return (Fn.pack_wino2d_packed(self.weights('gemm', 0), s.cout, s.cin, flip=False)
+                if fwd else None,
+                Fn.pack_wino2d_packed(self.weights('gemm', 1), s.cin, s.cout, flip=True)
+                if dgrad else None)
+
+    def weights(self, form, side, dtype=torch.float32):
+        """the forward (side 0) / data-gradient (side 1) operand of `form`: PackPlan's when fresh,
+        else re-packed -- the operands are rebuilt only when a parameter moved, and one side at a
+        time (a zero-fill and 2-4 small kernels per head and side)"""
+        return self.packs.get(form, dtype, side, self.key_now(),
+                              lambda fwd, dgrad: self._pack(form, dtype, fwd, dgrad), False)
+
+    def forward(self, x):
+        Fn.prof_flops(self.real_flops(x))
+        bias = self.weights('bias', 0) if self.has_bias else None
+        if x.dtype != torch.float32 or not self.wino:
+            return Fn.conv_fwd(x, self.weights('gemm', 0, x.dtype), self.spec, bias=bias)
+        if self.wino2d:
+            return Fn.conv_fwd(x, None, self.spec, bias=bias, wino_u=self.weights('wino', 0),
+                               wino2d_u=self.weights('wino2d', 0))
+        return Fn.conv_fwd(x, None, self.spec, bias=bias, wino_u=self.weights('wino', 0))
+
+    def real_flops(self, x):
+        """direct-convolution FLOPs of the REAL (un-padded, un-merged) convolutions on `x`"""
+        n, _, h, w = x.shape
+        return 2.0 * n * h * w * sum(m.weight.numel() for m, _, _ in self.placements)
+
+    def dgrad(self, dy, in_hw):
+        Fn.prof_flops(self.real_flops(dy))
+        if dy.dtype != torch.float32 or not self.wino:
+            return Fn.conv_dgrad(dy, self.weights('gemm', 1, dy.dtype), self.spec, in_hw)
+        if self.wino2d:
+            return Fn.conv_dgrad(dy, None, self.spec, in_hw, wino_u=self.weights('wino', 1),
+                                 wino2d_u=self.weights('wino2d', 1))
+        return Fn.conv_dgrad(dy, None, self.spec, in_hw, wino_u=self.weights('wino', 1))
 
     def params(self):
         ps = []

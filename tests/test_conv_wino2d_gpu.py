@@ -249,12 +249,16 @@ def test_wino2d_full_model_train_step(monkeypatch):
     r32, r64, out = o32(batch), o64(batch64), model(gbatch)
     for rt in rts2:
         u2, ud2 = Fn.pack_wino2d(rt.conv.weight.detach(), fwd=True, dgrad=True)
-        assert torch.equal(rt._u2, u2) and torch.equal(rt._ud2, ud2)
+        got_u2, got_ud2 = rt.packs.peek('wino2d', torch.float32, rt.key_now())
+        assert torch.equal(got_u2, u2) and torch.equal(got_ud2, ud2)
     for m in multi2:
         s = m.spec
-        assert m._key2 == m._key_now()
-        assert torch.equal(m._u2, Fn.pack_wino2d_packed(m._packed_fwd(), s.cout, s.cin, flip=False))
-        assert torch.equal(m._ud2, Fn.pack_wino2d_packed(m.packed_dgrad(), s.cin, s.cout, flip=True))
+        got_u2, got_ud2 = m.packs.peek('wino2d', torch.float32, m.key_now())
+        assert got_u2 is not None and got_ud2 is not None
+        assert torch.equal(got_u2, Fn.pack_wino2d_packed(m._assemble_fwd(torch.float32), s.cout, s.cin,
+                                                         flip=False))
+        assert torch.equal(got_ud2, Fn.pack_wino2d_packed(m._assemble_dgrad(torch.float32), s.cin, s.cout,
+                                                          flip=True))
     f32, f64, fo = T._flatten(r32), T._flatten(r64), T._flatten(out)
     assert len(f32) == len(fo) == len(f64)
     for i, (a, b, c) in enumerate(zip(fo, f32, f64)):

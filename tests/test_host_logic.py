@@ -310,6 +310,95 @@ def test_dry_run_bf16_training_groups_block_weight_gradients(generous_lib, monke
     assert c['emsa_conv1d_rs_t'] == 376
 
 
+# weight-transform launches of the first training step at 64x96, batch 2, without a PackPlan in front
+# (host tensors: the per-layer path): one per conv and form, forward and data-gradient side together
+_PACKS_FP32 = {'emsa_pack_wino': 195, 'emsa_pack_weight_pair': 27, 'emsa_pack_wino2d': 5,
+               'emsa_pack_wino_packed': 4, 'emsa_pack_wino2d_packed': 2}
+_PACKS_BF16 = {'emsa_pack_weight_frag_t': 188, 'emsa_pack_weight_t': 68}
+# placements of the merged heads, each assembled once per side: the 2-D Winograd head makes U and U2
+# from the same pair of operands (18 with an assembly of its own for U2)
+_ASSEMBLIES = 17
+
+
+@pytest.mark.parametrize('frozen', [False, True], ids=['trainable', 'layer1_frozen'])
+@pytest.mark.parametrize('dtype', ['float32', 'bfloat16'])
+def test_dry_run_packs_every_weight_form_once(dtype, frozen, monkeypatch):
+    """two training steps on unchanged weights: the first packs each form of each conv once (a frozen
+    Winograd / conv_rs conv in two launches, forward at the forward pass and data gradient when the
+    backward pass asks), the second finds everything cached -- frozen convs' data-gradient forms too"""
+    import emsanet_amd.model as M
+    from emsanet_amd import full_args
+    from oracle.emsanet_oracle import synthetic_batch
+    half = dtype != 'float32'
+    lib = _install(monkeypatch, _GenerousLib() if half else _FakeLib())
+    model = _model(full_args(input_height=64, input_width=96,
+                             **({'compute_dtype': dtype} if half else {}))).train()
+    n_frozen = 0
+    for k, p in model.named_parameters():
+        if frozen and 'encoder' in k and 'layer1' in k and 'conv' in k:
+            p.requires_grad_(False)
+            n_frozen += p.dim() == 4
+    assert n_frozen == (24 if frozen else 0)
+    monkeypatch.setattr(M.EMSANet, 'forward', _bypass_device_check(model))
+    steps = []
+    for _ in range(2):
+        n0 = len(lib.names)
+        outs = model(synthetic_batch(2, 64, 96))
+        flat = [t for o, sides in outs for t in (list(o) if isinstance(o, tuple) else [o])]
+        flat += [t for _, sides in outs for s in sides for t in (list(s) if isinstance(s, tuple) else [s])]
+        torch.autograd.backward(flat, [torch.zeros_like(t) for t in flat])
+        steps.append(collections.Counter(n for n in lib.names[n0:] if n.startswith('emsa_pack_')))
+    want = dict(_PACKS_BF16 if half else _PACKS_FP32)
+    want['emsa_pack_weight_frag_t' if half else 'emsa_pack_wino'] += n_frozen
+    if not half:
+        assert steps[0].pop('emsa_pack_weight_fwd') == _ASSEMBLIES <= 18
+        assert steps[0].pop('emsa_pack_weight_dgrad') == _ASSEMBLIES <= 18
+    assert dict(steps[0]) == want
+    assert not steps[1], steps[1]
+
+
+def test_pack_cache_rules():
+    """ops._PackCache: what a miss packs, what a hit returns, what `put` overwrites, what `peek` shows"""
+    from emsanet_amd.ops import _PackCache
+    calls = []
+
+    def pack(fwd, dgrad):
+        calls.append((fwd, dgrad))
+        n = len(calls)
+        return ('f%d' % n if fwd else None, 'd%d' % n if dgrad else None)
+    c, f32 = _PackCache(), torch.float32
+    assert c.peek('gemm', f32, 'k1') == (None, None)
+    # forward miss of a trainable weight: both sides from one call; then hits on either side
+    assert c.get('gemm', f32, 0, 'k1', pack, True) == 'f1' and calls == [(True, True)]
+    assert c.get('gemm', f32, 1, 'k1', pack, True) == 'd1' and c.get('gemm', f32, 0, 'k1', pack, True) == 'f1'
+    assert len(calls) == 1 and c.peek('gemm', f32, 'k1') == ('f1', 'd1')
+    # forward miss with both=False: the forward side alone; the data-gradient miss packs its side
+    # only, ONCE (a frozen weight's data-gradient form is cached like any other)
+    assert c.get('wino', f32, 0, 'k1', pack, False) == 'f2' and calls[-1] == (True, False)
+    assert c.peek('wino', f32, 'k1') == ('f2', None)
+    assert c.get('wino', f32, 1, 'k1', pack, False) == 'd3' and calls[-1] == (False, True)
+    assert c.get('wino', f32, 1, 'k1', pack, False) == 'd3' and c.get('wino', f32, 0, 'k1', pack, False) == 'f2'
+    assert len(calls) == 3 and c.peek('wino', f32, 'k1') == ('f2', 'd3')
+    # forms and dtypes are slots of their own
+    assert c.peek('wino', torch.bfloat16, 'k1') == (None, None) and c.peek('gemm', f32, 'k1') == ('f1', 'd1')
+    # key change: each side goes stale by its own key; a data-gradient miss does not touch the forward
+    assert c.peek('wino', f32, 'k2') == (None, None)
+    assert c.get('wino', f32, 1, 'k2', pack, False) == 'd4' and c.peek('wino', f32, 'k2') == (None, 'd4')
+    assert c.peek('wino', f32, 'k1') == ('f2', None)
+    assert c.get('wino', f32, 0, 'k2', pack, False) == 'f5' and c.peek('wino', f32, 'k2') == ('f5', 'd4')
+    # forward miss, both=False, beside a STALE data-gradient side: that one stays stale
+    assert c.get('wino', f32, 0, 'k3', pack, False) == 'f6' and c.peek('wino', f32, 'k3') == ('f6', None)
+    # put overwrites the whole slot; without a data-gradient side none survives under the new key
+    n = len(calls)
+    c.put('gemm', f32, 'k2', 'pf', 'pd')
+    assert c.peek('gemm', f32, 'k2') == ('pf', 'pd') and c.peek('gemm', f32, 'k1') == (None, None)
+    assert c.get('gemm', f32, 0, 'k2', pack, True) == 'pf' and c.get('gemm', f32, 1, 'k2', pack, True) == 'pd'
+    c.put('gemm', f32, 'k2', 'pf2', None)
+    assert c.peek('gemm', f32, 'k2') == ('pf2', None) and len(calls) == n
+    assert c.get('gemm', f32, 1, 'k2', pack, True) == 'd%d' % (n + 1) and calls[-1] == (False, True)
+    assert c.peek('gemm', f32, 'k2') == ('pf2', 'd%d' % (n + 1))
+
+
 def test_nbt1d_eval_pair_is_the_single_sequence_interleaved(fake_lib):
     """fp32 host tensors (no twin launch exists): the launches of nbt1d_eval_pair are those of the
     two nbt1d_eval calls, interleaved conv by conv; blocks that differ in their skip path are refused"""

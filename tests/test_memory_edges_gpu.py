@@ -402,9 +402,10 @@ def test_wgrad_multi_has_no_fp32_or_fp16_form(cfg, dtype, guard_allocations):
                                            (3, BF16, False)])
 def test_merged_head_repack_paths(k, dtype, wino2d, monkeypatch, guard_allocations):
     """ops.MultiConvRT without a PackPlan in front of it: the operand of two convs (5 + 2 output
-    channels in an 8-wide head) is assembled by its own re-pack paths -- `packed` / `packed_t` /
-    `packed_dgrad` / `_packed_fwd` (2-D Winograd) into zeroed buffers -- forward and data gradient
-    against the fp64 convs; the padding channel is the zero the buffers started with"""
+    channels in an 8-wide head) is assembled by its own re-pack paths -- `_assemble_fwd` /
+    `_assemble_dgrad`, in the activations' dtype, into zeroed buffers; U and U2 (2-D Winograd) are
+    made from those same two operands -- forward and data gradient against the fp64 convs; the
+    padding channel is the zero the buffers started with"""
     from emsanet_amd import ops
     Fn, A = _fn(), guard_allocations
     monkeypatch.setattr(Fn, 'WINO2D', wino2d)
@@ -433,11 +434,67 @@ def test_merged_head_repack_paths(k, dtype, wino2d, monkeypatch, guard_allocatio
     assert float(y[:, off:].float().abs().max()) == 0.0, 'padding channel of the merged head'
     dx = rt.dgrad(A.put(to_act(dy).to(dtype)), (h, w))
     close(dx, xd.grad, tol=tol, what='merged head dgrad')
-    sites = {e[3].rsplit(':', 1)[0] for e in A._live}
-    want = {'ops.py:packed_t' if lo else 'ops.py:packed', 'ops.py:packed_dgrad'}
+    sites = [(e[3].rsplit(':', 1)[0], e[5]) for e in A._live]
+    want = {('ops.py:_assemble_fwd', dtype), ('ops.py:_assemble_dgrad', dtype)}
     if rt.wino2d:
-        want.add('ops.py:_packed_fwd')
-    assert want <= sites, (want, sorted(s_ for s_ in sites if s_.startswith('ops.py')))
+        # U2 of both sides was made under the guard, from the operands the row form was made from
+        want.add(('functional.py:_wino2d_buf', F32))
+        assert rt.packs.peek('wino2d', F32, rt.key_now()) != (None, None)
+    assert want <= set(sites), (want, sorted(s_ for s_ in sites if s_[0].startswith('ops.py')))
+    for site in sorted(want):
+        # each operand is assembled once, whichever forms are made from it
+        assert sites.count(site) == (2 if site[0].startswith('functional.py') else 1), (site, sites)
+    A.check()
+
+
+@pytest.mark.parametrize('cin,cout,k,dtype,wino2d,shape,form', [
+    (64, 64, (3, 1), F32, None, (2, 6, 10), 'wino'),
+    (16, 8, (3, 3), F32, True, (2, 6, 10), 'wino2d'),
+    (12, 20, (3, 3), F32, True, (2, 5, 7), 'wino2d'),        # U2 with K-step padding
+    (16, 8, (1, 1), F32, None, (2, 6, 10), 'gemm'),
+    (64, 64, (3, 1), BF16, None, (2, 6, 10), None),          # 'frag', or 'gemm' where conv_rs refuses
+], ids=['wino', 'wino2d', 'wino2d-padded', 'gemm', 'bf16'])
+def test_frozen_conv_caches_its_data_gradient_pack(cin, cout, k, dtype, wino2d, shape, form, monkeypatch,
+                                                   guard_allocations):
+    """ops.ConvRT without a PackPlan in front of it, weight trainable / frozen: the same data
+    gradient bit for bit (== fp64), and the frozen conv's data-gradient operand -- packed at the
+    first request, the forward miss left it out -- is the SAME tensor at the second request"""
+    from emsanet_amd import ops
+    Fn, A = _fn(), guard_allocations
+    if wino2d is not None:
+        monkeypatch.setattr(Fn, 'WINO2D', wino2d)
+    n, h, w = shape
+    lo = dtype != F32
+    r_ = (lambda t: t.to(dtype).float()) if lo else (lambda t: t)
+    pad = (k[0] // 2, k[1] // 2)
+    conv = torch.nn.Conv2d(cin, cout, k, padding=pad, bias=False)
+    with torch.no_grad():
+        conv.weight.copy_(r_(rnd(cout, cin, *k, seed=3, scale=0.1)))
+    conv.to(DEV)
+    x, dy = r_(rnd(n, cin, h, w, seed=1)), r_(rnd(n, cout, h, w, seed=2))
+    xd = x.double().requires_grad_(True)
+    F.conv2d(xd, conv.weight.detach().cpu().double(), padding=pad).backward(dy.double())
+    gx, gdy = A.put(to_act(x).to(dtype)), A.put(to_act(dy).to(dtype))
+
+    def dgrad_packs(rt):
+        sides = {f: rt.packs.peek(f, dtype, rt.key_now())[1] for f in ('gemm', 'wino', 'wino2d', 'frag')}
+        return {f: t.data_ptr() for f, t in sides.items() if t is not None}
+    dxs = []
+    for trainable in (True, False):
+        conv.weight.requires_grad_(trainable)
+        rt = ops.ConvRT(conv)
+        assert rt.wino2d == bool(wino2d)
+        rt.forward(gx)
+        # the forward miss packed the data-gradient side along iff the weight is trainable
+        assert bool(dgrad_packs(rt)) == trainable
+        dx = rt.dgrad(gdy, (h, w))
+        packs = dgrad_packs(rt)
+        assert (form in packs) if form else bool(packs), packs
+        dx2 = rt.dgrad(gdy, (h, w))
+        assert torch.equal(dx, dx2) and dgrad_packs(rt) == packs
+        dxs.append(dx)
+    close(dxs[0], xd.grad, tol=TOL[dtype] if lo else 1e-4, what='data gradient')
+    assert torch.equal(dxs[0], dxs[1])
     A.check()
 
 

@@ -378,15 +378,18 @@ def test_pack_plan_matches_per_layer_transforms():
     assert len(plan.rts) > 200
     plan.refresh()
     n_wino = 0
+    F32, BF16 = torch.float32, torch.bfloat16
     for rt in plan.rts:
         w = rt.conv.weight.detach()
         if rt.wino:
             u, ud = Fn.pack_wino(w, fwd=True, dgrad=True)
-            assert torch.equal(rt._u, u) and torch.equal(rt._ud, ud)
+            got_u, got_ud = rt.packs.peek('wino', F32, rt.key_now())
+            assert torch.equal(got_u, u) and torch.equal(got_ud, ud)
             n_wino += 1
         else:
             wp, wpd = Fn.pack_weight_pair(w)
-            assert torch.equal(rt._wp, wp) and torch.equal(rt._wpd, wpd)
+            got_wp, got_wpd = rt.packs.peek('gemm', F32, rt.key_now())
+            assert torch.equal(got_wp, wp) and torch.equal(got_wpd, wpd)
     assert n_wino > 150
     # the merged / channel-padded head convs ride in the same launch: == their own re-pack path
     import copy as _copy
@@ -395,35 +398,44 @@ def test_pack_plan_matches_per_layer_transforms():
     for m in plan.multi:
         twin = ops.MultiConvRT(m.placements, m.spec.cout, m.spec.cin, (m.spec.kh, m.spec.kw),
                                (m.spec.ph, m.spec.pw))
-        wp, bias = twin.packed()
+        key = m.key_now()
+        wp, bias = twin.weights('gemm', 0), twin.weights('bias', 0) if twin.has_bias else None
+        m_wp, m_wpd = m.packs.peek('gemm', F32, key)
         if m.wino:
-            assert m._wp is None and torch.equal(m._u, twin._u)
-            ud = Fn.pack_wino_packed(twin.packed_dgrad(), m.spec.cin, m.spec.cout,
+            m_u, m_ud = m.packs.peek('wino', F32, key)
+            assert m_wp is None and torch.equal(m_u, twin.weights('wino', 0))
+            ud = Fn.pack_wino_packed(twin.weights('gemm', 1), m.spec.cin, m.spec.cout,
                                      Fn.wino_rows(m.spec), flip=True)
-            assert torch.equal(m._hd[torch.float32][2], ud)
+            assert torch.equal(m_ud, ud)
         else:
-            assert torch.equal(m._wp, wp) and torch.equal(m._hd[torch.float32][1], twin.packed_dgrad())
-        assert (bias is None) == (m._bias is None) and (bias is None or torch.equal(m._bias, bias))
-        assert m._key == m._key_now()
+            assert torch.equal(m_wp, wp) and torch.equal(m_wpd, twin.weights('gemm', 1))
+        m_bias = m.packs.peek('bias', F32, key)[0]
+        assert (bias is None) == (m_bias is None) and (bias is None or torch.equal(m_bias, bias))
+        assert m.packs.peek('wino' if m.wino else 'gemm', F32, key)[0] is not None
     plan.refresh(torch.bfloat16)
     for m in plan.multi:
         twin = ops.MultiConvRT(m.placements, m.spec.cout, m.spec.cin, (m.spec.kh, m.spec.kw),
                                (m.spec.ph, m.spec.pw))
-        wp16, _ = twin.packed_t(torch.bfloat16)
-        assert torch.equal(m._h[torch.bfloat16][1], wp16)
-        assert torch.equal(m._hd[torch.bfloat16][1], twin.packed_dgrad(torch.bfloat16))
+        m_wp16, m_wpd16 = m.packs.peek('gemm', BF16, m.key_now())
+        assert torch.equal(m_wp16, twin.weights('gemm', 0, BF16))
+        assert torch.equal(m_wpd16, twin.weights('gemm', 1, BF16))
     plan.refresh()
     rt = plan.rts[5]
-    before = rt._u.clone() if rt.wino else rt._wp.clone()
+    form = 'wino' if rt.wino else 'gemm'
+    before = rt.packs.peek(form, F32, rt.key_now())[0].clone()
     with torch.no_grad():
         rt.conv.weight.mul_(2.0)
+    assert rt.packs.peek(form, F32, rt.key_now()) == (None, None)      # stale until the refresh
     plan.refresh()
-    after = rt._u if rt.wino else rt._wp
+    after = rt.packs.peek(form, F32, rt.key_now())[0]
     assert torch.equal(after, before * 2.0)
     for p in model.parameters():
         p.requires_grad_(False)
     plan.refresh()
-    assert all((r._ud if r.wino else None) is None for r in plan.rts if r.wino)
+    for r in plan.rts:
+        if r.wino:
+            u, ud = r.packs.peek('wino', F32, r.key_now())
+            assert u is not None and ud is None
 
 
 def test_full_size_batch_consistency_and_determinism():

@@ -117,9 +117,10 @@ def test_fused_sgd_invalidates_packed_weight_caches():
     for rt in m1._pack_plan.rts[:40]:
         w = rt.conv.weight.detach()
         if rt.wino:
-            assert torch.equal(rt._u, Fn.pack_wino(w)[0])
+            assert torch.equal(rt.packs.peek('wino', torch.float32, rt.key_now())[0], Fn.pack_wino(w)[0])
         else:
-            assert torch.equal(rt._wp, Fn.pack_weight(w, 'fwd'))
+            assert torch.equal(rt.packs.peek('gemm', torch.float32, rt.key_now())[0],
+                               Fn.pack_weight(w, 'fwd'))
     for p1, p2 in zip(m1.parameters(), m2.parameters()):
         assert (p1 - p2).abs().max() <= 2e-6 * max(1.0, float(p2.abs().max()))
         changed += int(p1.grad is not None)
