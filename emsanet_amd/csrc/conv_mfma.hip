@@ -1136,24 +1136,67 @@ __global__ __launch_bounds__(256, XBN ? EMSA_W1DW_XBN_WPE : EMSA_W1DW_WPE) void 
       xbnS[tid] = ch < p.k_ch ? src[ch] : 0.f;
     }
   }
+  // LEAN (the fp32 instantiations): the step's pixel decomposition runs on the SCALAR unit.  The
+  // 32-pixel advance is wave-uniform, so pixel K1 = 32 (s + 1) -- the step's last -- is divided
+  // with scalar instructions, and lane l, which owns pixel K1 - d with d = 33 - l, subtracts a
+  // decomposition of d made ONCE per kernel: d = dI * (A L) + da * L + dr.  One borrow from b
+  // into a and one from a into the image suffice (|b1 - dr| < L, |a1 - da - 1| <= A), whatever
+  // the line length (2-, 15- and 20-pixel lines take several lines per step: they sit in da).
+  // The byte offsets follow without a multiply: base(K1) - c(d) + borrow terms.
+  constexpr bool LEAN = !BF16 && sizeof(T) == 4;
+  int ln_dr = 0, ln_da = 0;                 // per lane: dr, da
+  uint32_t ln_cd = 0, ln_cx = 0;            // per lane: dI * simg + da * sa + dr * sb in bytes (dy, x)
+  if constexpr (LEAN) {
+    const uint32_t d = lane < XROWS ? (uint32_t)(XROWS - 1 - lane) : 0u;
+    const uint32_t dI = fast_div(d, p.div_al), dLn = fast_div(d, p.div_l);
+    ln_dr = (int)(d - dLn * (uint32_t)p.L);
+    ln_da = (int)(dLn - dI * (uint32_t)p.A);
+    ln_cd = (dI * (uint32_t)p.dy_simg + (uint32_t)ln_da * (uint32_t)p.dy_sa +
+             (uint32_t)ln_dr * (uint32_t)p.dy_sb) * ES;
+    ln_cx = (dI * (uint32_t)p.in_simg + (uint32_t)ln_da * (uint32_t)p.in_sa +
+             (uint32_t)ln_dr * (uint32_t)p.in_sb) * ES;
+  }
   auto load_regs = [&](int s) {
     // lane l of every wave decomposes pixel k0 + l - 1 (l < 34) once; the loading threads fetch
     // their rows' byte offsets with wave shuffles
     const int k = s * PK + lane - 1;
     const bool valid = lane < XROWS && k >= 0 && k < p.M;
+    int b_, a2;
+    bool in_line;
+    uint32_t off_d, off_x;
+    if constexpr (LEAN) {
+      const uint32_t K1 = (uint32_t)__builtin_amdgcn_readfirstlane(s * PK + PK);   // wave-uniform
+      const uint32_t I1 = fast_div(K1, p.div_al), Ln1 = fast_div(K1, p.div_l);
+      const int b1 = (int)(K1 - Ln1 * (uint32_t)p.L), a1 = (int)(Ln1 - I1 * (uint32_t)p.A);
+      const uint32_t base_d = (I1 * (uint32_t)p.dy_simg + (uint32_t)a1 * (uint32_t)p.dy_sa +
+                               (uint32_t)b1 * (uint32_t)p.dy_sb) * ES;
+      const uint32_t base_x = (I1 * (uint32_t)p.in_simg + (uint32_t)(a1 + dline) * (uint32_t)p.in_sa +
+                               (uint32_t)b1 * (uint32_t)p.in_sb) * ES;
+      const uint32_t cb_d = (uint32_t)(p.L * p.dy_sb - p.dy_sa) * ES, ca_d = (uint32_t)(p.A * p.dy_sa - p.dy_simg) * ES;
+      const uint32_t cb_x = (uint32_t)(p.L * p.in_sb - p.in_sa) * ES, ca_x = (uint32_t)(p.A * p.in_sa - p.in_simg) * ES;
+      const int br = b1 - ln_dr, bm = br >> 31;              // bm = -1: borrow a line
+      b_ = br + (bm & p.L);
+      const int ar = a1 - ln_da + bm, am = ar >> 31;         // am = -1: borrow an image
+      a2 = ar + (am & p.A) + dline;
+      in_line = valid && b_ < p.Lr;
+      off_d = in_line ? base_d - ln_cd + ((uint32_t)bm & cb_d) + ((uint32_t)am & ca_d) : kOOB;
+      off_x = (in_line && a2 >= 0 && a2 < p.A)
+                  ? base_x - ln_cx + ((uint32_t)bm & cb_x) + ((uint32_t)am & ca_x) : kOOB;
+    } else {
     const uint32_t ku = valid ? (uint32_t)k : 0u;
     const uint32_t img = fast_div(ku, p.div_al);
     const uint32_t line = fast_div(ku, p.div_l);                 // = img * A + a
-    const int b_ = (int)(ku - __umul24(line, (uint32_t)p.L));
+    b_ = (int)(ku - __umul24(line, (uint32_t)p.L));
     const int a_ = (int)(line - __umul24(img, (uint32_t)p.A));
-    const int a2 = a_ + dline;
-    const bool in_line = valid && b_ < p.Lr;
-    const uint32_t off_d = in_line
+    a2 = a_ + dline;
+    in_line = valid && b_ < p.Lr;
+    off_d = in_line
         ? (__umul24(img, (uint32_t)p.dy_simg) + __umul24((uint32_t)a_, (uint32_t)p.dy_sa) +
            __umul24((uint32_t)b_, (uint32_t)p.dy_sb)) * ES : kOOB;
-    const uint32_t off_x = (in_line && a2 >= 0 && a2 < p.A)
+    off_x = (in_line && a2 >= 0 && a2 < p.A)
         ? (__umul24(img, (uint32_t)p.in_simg) + __umul24((uint32_t)a2, (uint32_t)p.in_sa) +
            __umul24((uint32_t)b_, (uint32_t)p.in_sb)) * ES : kOOB;
+    }
     // as the LEFT neighbour (d0) of the next pixel a line's last pixel reads zero, as the RIGHT
     // neighbour (d3) of the previous pixel a line's first pixel does: the tap crosses a line end
     const uint32_t off_xl = b_ == p.L - 1 ? kOOB : off_x;
@@ -1165,12 +1208,24 @@ __global__ __launch_bounds__(256, XBN ? EMSA_W1DW_XBN_WPE : EMSA_W1DW_WPE) void 
     const uint32_t o_d1 = (uint32_t)__builtin_amdgcn_ds_bpermute(l0 + 4, (int)off_x);
     const uint32_t o_d2 = (uint32_t)__builtin_amdgcn_ds_bpermute(l0 + 8, (int)off_x);
     const uint32_t o_d3 = (uint32_t)__builtin_amdgcn_ds_bpermute(l0 + 12, (int)off_xr);
+    if constexpr (LEAN) {
+      // channel column in ONE saturating add (v_add_u32 clamp): a dead column adds 0xFFFFFFFF, which
+      // saturates a live row to an offset beyond the tensor, and kOOB + a live column stays beyond it
+      const uint32_t dsat = dok ? dadd : 0xFFFFFFFFu, xsat = xok ? xadd : 0xFFFFFFFFu;
+      re_raw[0] = buf_ld4raw<T>(rs_dy, __builtin_elementwise_add_sat(o_e0, dsat));
+      re_raw[1] = buf_ld4raw<T>(rs_dy, __builtin_elementwise_add_sat(o_e1, dsat));
+      rx_raw[0] = buf_ld4raw<T>(rs_in, __builtin_elementwise_add_sat(o_d0, xsat));
+      rx_raw[1] = buf_ld4raw<T>(rs_in, __builtin_elementwise_add_sat(o_d1, xsat));
+      rx_raw[2] = buf_ld4raw<T>(rs_in, __builtin_elementwise_add_sat(o_d2, xsat));
+      rx_raw[3] = buf_ld4raw<T>(rs_in, __builtin_elementwise_add_sat(o_d3, xsat));
+    } else {
     re_raw[0] = buf_ld4raw<T>(rs_dy, (o_e0 + dadd) | dmask);
     re_raw[1] = buf_ld4raw<T>(rs_dy, (o_e1 + dadd) | dmask);
     rx_raw[0] = buf_ld4raw<T>(rs_in, (o_d0 + xadd) | xmask);
     rx_raw[1] = buf_ld4raw<T>(rs_in, (o_d1 + xadd) | xmask);
     rx_raw[2] = buf_ld4raw<T>(rs_in, (o_d2 + xadd) | xmask);
     rx_raw[3] = buf_ld4raw<T>(rs_in, (o_d3 + xadd) | xmask);
+    }
     if constexpr (XBN)
       x_real = (~o_d0 >> 31) | ((~o_d1 >> 31) << 1) | ((~o_d2 >> 31) << 2) | ((~o_d3 >> 31) << 3);
   };

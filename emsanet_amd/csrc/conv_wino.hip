@@ -17,7 +17,9 @@
 // prefetch (30 KiB -> 5 workgroups per CU).  The epilogue transposes m_j through LDS, applies the
 // output transform and the same fused epilogue as conv_igemm (bias, BatchNorm statistics
 // partials, folded BatchNorm, residual, ReLU, ReLU-backward mask) with 16-B stores.
+#include <atomic>
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.h"
 #include "prof.h"
@@ -117,8 +119,29 @@ __device__ __forceinline__ uint32_t wdiv(uint32_t n, uint32_t mul, uint32_t sh) 
 // INBN: the input's BatchNorm + ReLU applied where the K step enters LDS (WinoArgs::in_scale); 1-D
 // convs only (R = 1).  Costs 12 vector instructions per K step and thread (2 packed FMAs + 4
 // v_med3 per float4: max(v, 0) and the zero-padding mask in one instruction, cap = +inf / 0).
-template <int kWN, bool BF16 = false, bool BNB = false, bool INBN = false>   // kWN: output channels per workgroup, 64 (2 MFMA tiles per wave) or 32
+// OPT: the epilogue's feature set as a compile-time constant (bits kO*), or -1 = the generic
+// kernel, which reads the options from WinoArgs at run time.  The compiler if-converts run-time
+// options into selects, so an ABSENT option still costs instructions on each of the thread's four
+// pixels -- and every one of them is four cycles the fp32 MFMA pipe does not get.
+// A specialised instantiation emits nothing for the features it lacks, and additionally assumes
+// what its dispatch guarantees (wino_spec_opt): R = 1, c_in a multiple of kWK (no channel-tail
+// mask in the K loop), no folded output scale / shift, no float mask_src (BNB: both present).
+enum : int {
+  kOBias = 1, kORelu = 2, kORBits = 4, kOStats = 8, kOMBits = 16, kORes = 32, kOMRes = 64
+};
+template <int kWN, bool BF16 = false, bool BNB = false, bool INBN = false, int OPT = -1>   // kWN: output channels per workgroup, 64 (2 MFMA tiles per wave) or 32
 __global__ __launch_bounds__(256, kWN == 64 ? (BNB ? 4 : 5) : 6) void conv1d_wino_kernel(const WinoArgs p) {
+  constexpr bool SPEC = OPT >= 0;
+  static_assert(!SPEC || (kWN == 64 && !BF16), "specialised epilogues: fp32, 64-channel tiles");
+  const bool f_bias = SPEC ? (OPT & kOBias) != 0 : p.bias != nullptr;
+  const bool f_relu = SPEC ? (OPT & kORelu) != 0 : p.act == EMSA_ACT_RELU;
+  const bool f_rbits = SPEC ? (OPT & kORBits) != 0 : p.relu_bits != nullptr;
+  const bool f_stats = SPEC ? (OPT & kOStats) != 0 : p.stats != nullptr;
+  const bool f_mbits = SPEC ? (OPT & kOMBits) != 0 : p.mask_bits != nullptr;
+  const bool f_res = SPEC ? (OPT & kORes) != 0 : p.residual != nullptr;
+  const bool f_mres = SPEC ? (OPT & kOMRes) != 0 : p.mask_res != 0;
+  const bool f_scale = SPEC ? BNB : p.scale != nullptr;
+  const bool f_msrc = SPEC ? BNB : p.mask_src != nullptr;
   constexpr int NT = kWN / 32;                    // accumulator tiles per wave
   constexpr int NC4 = kWN / 4;                    // float4 columns of a tile row
   constexpr int RG = 256 / NC4;                   // pixel rows covered by one pass of the block
@@ -173,7 +196,26 @@ __global__ __launch_bounds__(256, kWN == 64 ? (BNB ? 4 : 5) : 6) void conv1d_win
       a_line[j] = al;
     }
   };
-  setup_a(mt);
+  if constexpr (SPEC) {
+    // a thread's two rows belong to the SAME pair (rowid = pair + 32 * rr, rr = tid / 128 + 2 j):
+    // one decomposition, and with R = 1 the tile's offsets are final (no set_row)
+    const int rr0 = tid >> 7, q = q0 + ((tid >> 2) & 31);
+    a_voff[0] = a_voff[1] = kOOBw;
+    if (q < p.MP) {
+      const int line = (int)wdiv((uint32_t)q, p.mul_pl, p.sh_pl);
+      const int pp = q - line * p.PL;
+      const int img = (int)wdiv((uint32_t)line, p.mul_a, p.sh_a);
+      const int a = line - img * p.A;
+      const int base = img * p.in_simg + a * p.in_sa + c4;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int b = 2 * pp - 1 + rr0 + 2 * j;
+        if (b >= 0 && b < p.L) a_voff[j] = (uint32_t)(base + b * p.in_sb) * 4u;
+      }
+    }
+  } else {
+    setup_a(mt);
+  }
 #pragma unroll
   for (int j = 0; j < BLD; ++j) {
     const int rowid = (tid >> 2) + 64 * j;          // 0..4*kWN-1 = comp*kWN + n
@@ -183,7 +225,7 @@ __global__ __launch_bounds__(256, kWN == 64 ? (BNB ? 4 : 5) : 6) void conv1d_win
   // offsets of the tile's pixels on kernel row r (r = 0 only for the 1-D convs): the line shifts
   // by r - 1 and may leave the image (zero padding)
   auto set_row = [&](int r) {
-    const int dr = p.R == 3 ? r - 1 : 0;
+    const int dr = !SPEC && p.R == 3 ? r - 1 : 0;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int al = a_line[j] + dr;
@@ -195,6 +237,15 @@ __global__ __launch_bounds__(256, kWN == 64 ? (BNB ? 4 : 5) : 6) void conv1d_win
   const uint32_t last_oob = (p.ksteps_c - 1) * kWK + c4 < p.c_in ? 0u : kOOBw;
   float4 ra[2], rb[BLD];
   auto load_regs = [&](int s) {
+    if constexpr (SPEC) {
+      // one tap row, whole channel chunks: the step is a scalar offset and nothing else
+      const uint32_t so = (uint32_t)(s * kWK) * 4u;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) ra[j] = wbuf_ld4s(rs_in, a_voff[j], so);
+#pragma unroll
+      for (int j = 0; j < BLD; ++j) rb[j] = wbuf_ld4s(rs_u, b_voff[j], so);
+      return;
+    }
     // K step s = (perpendicular tap r, channel chunk), all wave-uniform
     const int r = s >= 2 * p.ksteps_c ? 2 : (s >= p.ksteps_c ? 1 : 0);
     const int ch = (s - r * p.ksteps_c) * kWK;                     // first input channel
@@ -243,10 +294,13 @@ __global__ __launch_bounds__(256, kWN == 64 ? (BNB ? 4 : 5) : 6) void conv1d_win
 
   load_regs(0);
   f32x16 acc[NT];
+  // (SPEC: the first K step's MFMAs take a zero C operand instead -- 32 v_mov less)
+  if constexpr (!SPEC) {
 #pragma unroll
-  for (int t = 0; t < NT; ++t)
+    for (int t = 0; t < NT; ++t)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+      for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+  }
 
   if constexpr (INBN) {
     // the affine table of all input channels (zeros beyond c_in: those K entries meet zero
@@ -260,7 +314,8 @@ __global__ __launch_bounds__(256, kWN == 64 ? (BNB ? 4 : 5) : 6) void conv1d_win
   }
   store_lds(0);
   __syncthreads();
-  for (int s = 0; s < p.ksteps; ++s) {
+  auto kstep = [&](int s, auto first_c) {
+    constexpr bool first = decltype(first_c)::value;   // SPEC only: the tile's first K step
     const bool has_next = s + 1 < p.ksteps;
 #if EMSA_WINO_PRIO == 2
     __builtin_amdgcn_s_setprio(3);           // the next step's loads go out first
@@ -307,8 +362,15 @@ __global__ __launch_bounds__(256, kWN == 64 ? (BNB ? 4 : 5) : 6) void conv1d_win
 #pragma unroll
       for (int u = 0; u < NT; ++u) fb[u] = emsa_ld4(b + u * 32 * kWLD + co);
 #pragma unroll
-      for (int u = 0; u < NT; ++u)
-        acc[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(v.x, fb[u].x, acc[u], 0, 0, 0);
+      for (int u = 0; u < NT; ++u) {
+        if (first && t == 0) {
+          const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f,
+                               0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+          acc[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(v.x, fb[u].x, zero, 0, 0, 0);
+        } else {
+          acc[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(v.x, fb[u].x, acc[u], 0, 0, 0);
+        }
+      }
 #pragma unroll
       for (int u = 0; u < NT; ++u)
         acc[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(v.y, fb[u].y, acc[u], 0, 0, 0);
@@ -326,6 +388,12 @@ __global__ __launch_bounds__(256, kWN == 64 ? (BNB ? 4 : 5) : 6) void conv1d_win
     __syncthreads();
     if (has_next) store_lds(s + 1);
     __syncthreads();
+  };
+  if constexpr (SPEC) {
+    kstep(0, std::true_type{});
+    for (int s = 1; s < p.ksteps; ++s) kstep(s, std::false_type{});
+  } else {
+    for (int s = 0; s < p.ksteps; ++s) kstep(s, std::false_type{});
   }
 
   // ---- epilogue: m_j -> LDS, output transform, fused epilogue ---------------------------------
@@ -359,7 +427,7 @@ __global__ __launch_bounds__(256, kWN == 64 ? (BNB ? 4 : 5) : 6) void conv1d_win
   wf32x2 ylo[PXI], yhi[PXI];
   uint32_t opix[PXI];          // pixel index (< 2^29, checked by emsa_conv1d_wino_supported)
   bool ok[PXI];
-  const float4 bv = (nok && p.bias) ? emsa_ld4(p.bias + n) : emsa_zero4();
+  const float4 bv = (nok && f_bias) ? emsa_ld4(p.bias + n) : emsa_zero4();
   const wf32x2 blo = {bv.x, bv.y}, bhi = {bv.z, bv.w};
   // out(e=0) = m0 + m1 + m2, out(e=1) = m1 - m2 - m3  ==  m1 + sg * (m2 + m03); e = px & 1 is a
   // per-thread constant (RG is even)
@@ -388,12 +456,12 @@ __global__ __launch_bounds__(256, kWN == 64 ? (BNB ? 4 : 5) : 6) void conv1d_win
 #pragma unroll
   for (int k = 0; k < PXI; ++k) {
     const bool live = ok[k];
-    if (p.residual)
+    if (f_res)
       rres[k] = wbuf_ld4(rs_res, live ? (opix[k] * (uint32_t)p.ld_res + (uint32_t)n) * 4u : kOOBw);
-    if (p.mask_src)
+    if (f_msrc)
       rmsk[k] = wbuf_ld4(rs_msk, live ? (opix[k] * (uint32_t)p.ld_mask + (uint32_t)n) * 4u : kOOBw);
     if constexpr (kWN == 64) {
-      if (p.mask_bits)
+      if (f_mbits)
         rbits[k] = __builtin_bit_cast(
             wu32x2, __builtin_amdgcn_raw_buffer_load_b64(
                         rs_mb, (int)(live ? (opix[k] * (uint32_t)p.tiles_n + (uint32_t)nt) * 8u
@@ -420,12 +488,18 @@ __global__ __launch_bounds__(256, kWN == 64 ? (BNB ? 4 : 5) : 6) void conv1d_win
     const float4 m03 = emsa_ld4(stage + (m03row * HP + prl) * SLD + col4 * 4);
     const wf32x2 tlo = wf32x2{m2.x, m2.y} + wf32x2{m03.x, m03.y};
     const wf32x2 thi = wf32x2{m2.z, m2.w} + wf32x2{m03.z, m03.w};
-    ylo[k] = __builtin_elementwise_fma(tlo, sg2o, wf32x2{m1.x, m1.y}) + blo;
-    yhi[k] = __builtin_elementwise_fma(thi, sg2o, wf32x2{m1.z, m1.w}) + bhi;
+    ylo[k] = __builtin_elementwise_fma(tlo, sg2o, wf32x2{m1.x, m1.y});
+    yhi[k] = __builtin_elementwise_fma(thi, sg2o, wf32x2{m1.z, m1.w});
+    // (without a bias the generic kernel adds +0, which changes -0 only -- and the fma above never
+    // yields -0: the accumulators start from +0 and x + (-0) keeps x, so m1 is never -0)
+    if (!SPEC || f_bias) {
+      ylo[k] += blo;
+      yhi[k] += bhi;
+    }
   }
   }   // halves
 
-  if (p.stats != nullptr) {
+  if (f_stats) {
     // per-tile (sum, M2 about the tile mean, count) over the tile's VALID output pixels
     __syncthreads();                               // everyone has read `stage`
     float* red = smem;                             // [RG row groups][kWN]
@@ -485,8 +559,8 @@ __global__ __launch_bounds__(256, kWN == 64 ? (BNB ? 4 : 5) : 6) void conv1d_win
   {
     wf32x2 sclo = {1.f, 1.f}, schi = {1.f, 1.f}, shlo = {0.f, 0.f}, shhi = {0.f, 0.f};
     constexpr bool bnb = BNB;
-    const bool affine = p.scale != nullptr && !bnb;
-    if (p.scale != nullptr && nok) {
+    const bool affine = f_scale && !bnb;
+    if (f_scale && nok) {
       const float4 sc = emsa_ld4(p.scale + n), sh = emsa_ld4(p.shift + n);
       sclo = wf32x2{sc.x, sc.y}; schi = wf32x2{sc.z, sc.w};
       shlo = wf32x2{sh.x, sh.y}; shhi = wf32x2{sh.z, sh.w};
@@ -514,10 +588,10 @@ __global__ __launch_bounds__(256, kWN == 64 ? (BNB ? 4 : 5) : 6) void conv1d_win
         q.z = __uint_as_float(__float_as_uint(q.z) & (uint32_t)__builtin_amdgcn_sbfe((int)t1, 0, 1));
         q.w = __uint_as_float(__float_as_uint(q.w) & (uint32_t)__builtin_amdgcn_sbfe((int)t1, 16, 1));
       };
-      if (p.residual) {
+      if (f_res) {
         float4 rr = rres[k];
         if constexpr (kWN == 64) {
-          if (p.mask_res) gate(rr);
+          if (f_mres) gate(rr);
         }
         vlo += wf32x2{rr.x, rr.y};
         vhi += wf32x2{rr.z, rr.w};
@@ -535,15 +609,26 @@ __global__ __launch_bounds__(256, kWN == 64 ? (BNB ? 4 : 5) : 6) void conv1d_win
         b0lo += glo; b0hi += ghi;
         b1lo = __builtin_elementwise_fma(glo, wf32x2{tt.x, tt.y} - mulo, b1lo);
         b1hi = __builtin_elementwise_fma(ghi, wf32x2{tt.z, tt.w} - muhi, b1hi);
-      } else if (p.mask_src) {
+      } else if (f_msrc) {
         const float4 mm = rmsk[k];
         v.x = mm.x > 0.f ? v.x : 0.f; v.y = mm.y > 0.f ? v.y : 0.f;
         v.z = mm.z > 0.f ? v.z : 0.f; v.w = mm.w > 0.f ? v.w : 0.f;
       }
       if constexpr (kWN == 64) {
-        if (p.mask_bits && !p.mask_res) gate(v);
+        if (f_mbits && !f_mres) gate(v);
       }
-      if (p.act == EMSA_ACT_RELU) {
+      if constexpr (SPEC) {
+        // one v_med3 per element (fmaxf costs two v_max: the compiler canonicalises its operand
+        // first); med3(v, 0, +inf) = max(v, 0), and 0 for a QUIET NaN like fmaxf.  A signalling
+        // NaN would come out quiet instead of 0 (IEEE mode), but v cannot be one: on every path
+        // of the specialised sets it is the result of a v_pk_fma / v_pk_add (output transform,
+        // bias), which quiets
+        if (f_relu) {
+          const float inf = __uint_as_float(0x7F800000u);
+          v.x = __builtin_amdgcn_fmed3f(v.x, 0.f, inf); v.y = __builtin_amdgcn_fmed3f(v.y, 0.f, inf);
+          v.z = __builtin_amdgcn_fmed3f(v.z, 0.f, inf); v.w = __builtin_amdgcn_fmed3f(v.w, 0.f, inf);
+        }
+      } else if (f_relu) {
         v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f);
         v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
       }
@@ -552,8 +637,30 @@ __global__ __launch_bounds__(256, kWN == 64 ? (BNB ? 4 : 5) : 6) void conv1d_win
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4w, v), rs_out, (int)off, 0,
                                                EMSA_WINO_ST_AUX);
       }
-      if constexpr (kWN == 64) {
-        if (p.relu_bits) {                           // uniform branch: ballots see every lane
+      if constexpr (SPEC) {
+        if (f_rbits) {
+          // compares land in SGPR pairs; each lane shifts its pixel's 16-bit field of the four
+          // ballots down (one v_lshrrev_b64 each) and two v_perm_b32 merge them into the word,
+          // stored through a 32-bit buffer offset (< 2 GiB: checked by the launcher).  No AND
+          // with `live`: a pixel outside the tensor stores no word, and a channel column beyond
+          // n_ch holds relu(0 + 0) = 0 (its weight rows and its bias read as zero; a NaN input
+          // gives relu(NaN) = 0) -- never > 0.
+          const uint64_t b0 = __builtin_amdgcn_ballot_w64(v.x > 0.f);
+          const uint64_t b1 = __builtin_amdgcn_ballot_w64(v.y > 0.f);
+          const uint64_t b2 = __builtin_amdgcn_ballot_w64(v.z > 0.f);
+          const uint64_t b3 = __builtin_amdgcn_ballot_w64(v.w > 0.f);
+          const int sh16 = (lane >> 4) * 16;         // this pixel's 16 lanes within the wave
+          const uint32_t t0 = (uint32_t)(b0 >> sh16), t1 = (uint32_t)(b1 >> sh16);
+          const uint32_t t2 = (uint32_t)(b2 >> sh16), t3 = (uint32_t)(b3 >> sh16);
+          // v_perm_b32: bytes 0..3 = second operand, 4..7 = first -> (t1 << 16) | (t0 & 0xFFFF)
+          const wu32x2 word = {__builtin_amdgcn_perm(t1, t0, 0x05040100u),
+                               __builtin_amdgcn_perm(t3, t2, 0x05040100u)};
+          const uint32_t boff = (col4 == 0 && opix[k] != kNoPix)
+                                    ? (opix[k] * (uint32_t)p.tiles_n + (uint32_t)nt) * 8u : kOOBw;
+          __builtin_amdgcn_raw_buffer_store_b64(word, wrsrc(p.relu_bits, kOOBw), (int)boff, 0, 0);
+        }
+      } else if constexpr (kWN == 64) {
+        if (f_rbits) {                           // uniform branch: ballots see every lane
           const uint64_t b0 = __ballot(live && v.x > 0.f), b1 = __ballot(live && v.y > 0.f);
           const uint64_t b2 = __ballot(live && v.z > 0.f), b3 = __ballot(live && v.w > 0.f);
           const int sh16 = (lane >> 4) * 16;         // this pixel's 16 lanes within the wave
@@ -869,6 +976,41 @@ static int wino_wn() {
   return forced_wn == 32 || forced_wn == 64 ? forced_wn : 64;
 }
 
+// EMSA_WINO_SPEC=0 (read once) or emsa_conv1d_wino_set_spec(0): every launch takes the generic
+// kernel (the reference of tests/test_wino_spec_gpu.py)
+// (relaxed atomics: host threads may launch convs concurrently)
+static std::atomic<int> g_wino_spec{[] {
+  const char* e = getenv("EMSA_WINO_SPEC");
+  return e && e[0] == '0' ? 0 : 1;
+}()};
+static std::atomic<int> g_wino_spec_launches{0};
+extern "C" int emsa_conv1d_wino_set_spec(int32_t on) {
+  return g_wino_spec.exchange(on ? 1 : 0, std::memory_order_relaxed);
+}
+// launches of this process that took a specialised instantiation (what the dispatch tests read)
+extern "C" int emsa_conv1d_wino_spec_launches(void) {
+  return g_wino_spec_launches.load(std::memory_order_relaxed);
+}
+
+// key of a specialised instantiation: its feature bits plus the BNB / INBN template flags
+constexpr int wino_spec_key(bool bnb, bool inbn, int opt) {
+  return opt | (bnb ? 0x100 : 0) | (inbn ? 0x200 : 0);
+}
+// the key this launch asks for, or -1 where it needs what only the generic kernel has: a folded
+// output scale / shift, a float mask_src (both allowed with BNB, which requires them), a 32-channel
+// tile, BF16 MFMAs, the three-row form, a partial last channel chunk
+static int wino_spec_opt(const WinoArgs& a, int wn, bool bf16) {
+  if (!g_wino_spec.load(std::memory_order_relaxed) || wn != 64 || bf16 || a.R != 1 || (a.c_in % kWK)) return -1;
+  const bool bnb = a.bnb_out != nullptr;
+  if (!bnb && (a.scale || a.mask_src)) return -1;
+  if (a.act != EMSA_ACT_NONE && a.act != EMSA_ACT_RELU) return -1;
+  const int opt = (a.bias ? kOBias : 0) | (a.act == EMSA_ACT_RELU ? kORelu : 0) |
+                  (a.relu_bits ? kORBits : 0) | (a.stats ? kOStats : 0) |
+                  (a.mask_bits ? kOMBits : 0) | (a.residual ? kORes : 0) |
+                  (a.mask_res ? kOMRes : 0);
+  return wino_spec_key(bnb, a.in_scale != nullptr, opt);
+}
+
 static int conv1d_wino_impl(const EmsaConvGeom* g, const float* in, const float* u, float* out,
                             const float* bias, float* stats, const float* scale,
                             const float* shift, const float* residual, int32_t ld_res,
@@ -951,7 +1093,29 @@ static int conv1d_wino_impl(const EmsaConvGeom* g, const float* in, const float*
     const char* e = getenv("EMSA_BF16_MFMA");
     return e && e[0] == '1';
   }();
-  if (in_scale) {
+  const dim3 grid(a.tiles_m * a.tiles_n);
+#define EMSA_WINO_SPEC_CASE(BNB_, INBN_, OPT_)                                                     \
+  case wino_spec_key(BNB_, INBN_, OPT_):                                                           \
+    hipLaunchKernelGGL((conv1d_wino_kernel<64, false, BNB_, INBN_, OPT_>), grid, dim3(256), lds,   \
+                       (hipStream_t)stream, a);                                                    \
+    break;
+  bool launched = true;
+  switch (wino_spec_opt(a, wn, bf16)) {
+    // the feature sets an NBt1D block's training step launches
+    EMSA_WINO_SPEC_CASE(false, false, kOBias | kORelu | kORBits)
+    EMSA_WINO_SPEC_CASE(false, true, kOBias | kORelu | kORBits)
+    EMSA_WINO_SPEC_CASE(false, false, kOBias | kOStats)
+    EMSA_WINO_SPEC_CASE(false, false, kOMBits)
+    EMSA_WINO_SPEC_CASE(false, false, kORes | kOMBits | kOMRes)
+    EMSA_WINO_SPEC_CASE(false, false, 0)
+    EMSA_WINO_SPEC_CASE(true, false, 0)
+    EMSA_WINO_SPEC_CASE(true, false, kORes)
+    default: launched = false;
+  }
+#undef EMSA_WINO_SPEC_CASE
+  if (launched) {
+    g_wino_spec_launches.fetch_add(1, std::memory_order_relaxed);
+  } else if (in_scale) {
     hipLaunchKernelGGL((conv1d_wino_kernel<64, false, false, true>),
                        dim3(a.tiles_m * a.tiles_n), dim3(256), lds, (hipStream_t)stream, a);
   } else if (bnb_out) {

@@ -166,6 +166,14 @@ int emsa_conv1d_wino_bnb(const EmsaConvGeom* g, const float* dy, const float* u,
  * masked residual (an NBt1D block's skip gradient dout * (out > 0)) is never stored.
  * emsa_conv1d_wino_resmask_supported: 1 where the launch takes (g, ld_res) -- a geometry of
  * emsa_conv1d_wino_supported with n_ch % 64 == 0 --, decided on the host without a launch.        */
+/* emsa_conv1d_wino* pick a kernel instantiation with a compile-time epilogue for the operand
+ * combinations of the training step (same results, fewer vector instructions); on = 0 makes every
+ * later launch of this process take the generic kernel, on = 1 restores the choice.  Returns the
+ * previous setting.  EMSA_WINO_SPEC=0 in the environment starts the process with 0.
+ * emsa_conv1d_wino_spec_launches: how many launches of this process took a specialised
+ * instantiation so far (tests read it to see which kernel the dispatch chose).                   */
+int emsa_conv1d_wino_set_spec(int32_t on);
+int emsa_conv1d_wino_spec_launches(void);
 int emsa_conv1d_wino_resmask_supported(const EmsaConvGeom* g, int32_t ld_res);
 int emsa_conv1d_wino_resmask(const EmsaConvGeom* g, const float* dy, const float* u, float* out,
                              const float* residual, int32_t ld_res, const uint64_t* res_bits,
