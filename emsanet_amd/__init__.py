@@ -34,4 +34,7 @@ def __getattr__(name):
     if name in ('InferenceOutputPacker', 'write_mapping_output'):
         from . import export
         return getattr(export, name)
+    if name in ('PngEncoder', 'write_scannet_output'):
+        from . import png
+        return getattr(png, name)
     raise AttributeError(name)

@@ -204,6 +204,9 @@ SIGNATURES = {
                                            _P, _P]),
     'emsa_export_instance_masks': (c_int, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                            _P, c_int32, _P, _P, c_int32, _P, _P]),
+    'emsa_png_bound': (c_int64, [c_int32, c_int32, c_int32]),
+    'emsa_png_ws_bytes': (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    'emsa_png_encode': (c_int, [_P, c_int32, c_int32, c_int32, c_int32, _P, c_int64, _P, _P, _P]),
     'emsa_targets_workspace_bytes': (c_int64, [c_int32, c_int32, c_int32]),
     'emsa_targets_table_entries': (c_int, [c_int32]),
     'emsa_targets_stats': (c_int, [_P, c_int32, _P, c_int32, _P, c_int32, c_int32, c_int32, c_int32, _TP,

@@ -52,8 +52,9 @@ packed as documented in include/emsanet_hip.h; `check()` raises ValueError namin
 has to know the number of instances on the host to size the stack: it is the ONE call here that
 synchronises.
 
-PNG encoding stays with the caller (no image codec is a dependency); the arrays have exactly the
-layout `cv2.imwrite` is given in the reference.
+The arrays have exactly the layout `cv2.imwrite` is given in the reference.  The `scannet_*` outputs and
+the mask planes become PNG files on the device with `emsanet_amd/png.py` (`PngEncoder.encode_packed`,
+`write_scannet_output`); no image codec is a dependency.
 """
 import json
 import os

@@ -974,6 +974,36 @@ int emsa_export_instance_masks(const void* instance, int32_t instance_dtype, int
                                uint8_t* stack, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * PNG encoding on the device (csrc/png.hip): what the reference's dataset inference run writes with
+ * cv2.imwrite for every `scannet-*` output, made from the dense stacks of emsa_export_pack /
+ * emsa_export_instance_masks where they lie.  Each of the m images [h][w] becomes one complete PNG
+ * file (signature, IHDR, one IDAT chunk per strip of 4 rows, IEND; filter 0, one zlib stream of
+ * fixed-Huffman blocks whose only matches are runs of equal pixels, every CRC-32 and the Adler-32
+ * computed on the device).  Layouts:
+ *     EMSA_PNG_GRAY8    uint8  [m][h][w]      colour type 0, depth 8
+ *     EMSA_PNG_BGR8     uint8  [m][h][w][3]   B, G, R in memory (as cv2.imwrite is given); colour
+ *                                             type 2, depth 8, stored R, G, B
+ *     EMSA_PNG_GRAY16   uint16 [m][h][w]      colour type 0, depth 16, stored big-endian
+ *   emsa_png_bound      the most bytes one file can take (incompressible input: 9 bits per literal,
+ *                       the flush of every strip, all framing); EMSA_E_SHAPE for a bad geometry.
+ *   emsa_png_ws_bytes   scratch bytes of emsa_png_encode (one worst-case slot per strip).
+ *   emsa_png_encode     launches only (three kernels): no allocation, copy or synchronisation.
+ *       data uint8[data_bytes] (DEVICE), data_bytes >= m * emsa_png_bound (EMSA_E_SHAPE otherwise);
+ *       offsets int64[m + 1] (DEVICE): file i is data[offsets[i] : offsets[i + 1]], offsets[0] = 0, the
+ *       files are contiguous; no byte at or behind offsets[m] is written.  ws 16-byte aligned.
+ *       h, w in [1, EMSA_PNG_MAX_SIDE], m in [1, 65535]; the geometry is checked before the pointers.
+ *       The bytes are a pure function of the input (two encodes of one stack are byte-equal).
+ * ------------------------------------------------------------------------------------------ */
+#define EMSA_PNG_GRAY8 0
+#define EMSA_PNG_BGR8 1
+#define EMSA_PNG_GRAY16 2
+#define EMSA_PNG_MAX_SIDE 4096
+int64_t emsa_png_bound(int32_t layout, int32_t h, int32_t w);
+int64_t emsa_png_ws_bytes(int32_t layout, int32_t m, int32_t h, int32_t w);
+int emsa_png_encode(const void* src, int32_t layout, int32_t m, int32_t h, int32_t w, uint8_t* data,
+                    int64_t data_bytes, int64_t* offsets, void* ws, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * 16-bit convolution family (BASELINE configs[2] bf16 mixed-precision training, configs[4] 16-bit
  * inference; the reference trains / times fp32 and fp16-TensorRT, README.md:176-181).
  *
