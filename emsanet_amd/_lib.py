@@ -22,6 +22,16 @@ class EmsaPackJob(Structure):
                 ('cin_total', c_int32), ('cin_off', c_int32)]
 
 
+# EmsaPackJob.kind, the numbering of emsa_pack_batch (include/emsanet_hip.h); the 16-bit kinds by the
+# EMSA_DT_* code of the result (1 = bf16, 2 = fp16)
+PACK_GEMM = 0                      # OIHW -> fp32 [tap][n][k], forward and data gradient
+PACK_WINO = 1                      # OIHW -> Winograd F(2,3) U, both sides
+PACK_GEMM_16 = {1: 2, 2: 3}        # OIHW -> 16-bit [tap][n][k]
+PACK_COPY = 4                      # `cout` floats (a bias vector) to dst0 + cout_off
+PACK_FRAG_16 = {1: 5, 2: 6}        # OIHW -> fragment-ordered 16-bit operands of conv_rs.hip
+PACK_WINO2D = 7                    # OIHW 3x3 -> Winograd F(2x2,3x3) U2, both sides
+
+
 class EmsaDropoutJob(Structure):
     _fields_ = [('offset', c_int64), ('c', c_int32), ('layer_id', c_uint32), ('p', c_float),
                 ('pad_', c_int32)]

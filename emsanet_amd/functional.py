@@ -335,6 +335,12 @@ def wino_eligible(spec):
     return shape and spec.sh == 1 and spec.sw == 1 and spec.cin % 4 == 0 and spec.cout % 4 == 0
 
 
+def wino_enabled(spec):
+    """an eligible conv keeps and runs the Winograd form (EMSA_WINO=0: every conv on the implicit GEMM);
+    asked when a runtime is constructed"""
+    return wino_eligible(spec) and os.environ.get('EMSA_WINO', '1') != '0'
+
+
 def wino_rows(spec):
     return 3 if (spec.kh, spec.kw) == (3, 3) else 1
 

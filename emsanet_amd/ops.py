@@ -108,6 +108,28 @@ class _PackCache:
         return ent[1] if ent[0] == key else None, ent[3] if ent[2] == key else None
 
 
+# One packed form of a conv's weights as a packer has to know it: the slot's name in `_PackCache`, the
+# EmsaPackJob kind (None: no job of emsa_pack_batch makes it, the runtime derives it itself), the
+# element type of the result, the elements of the forward and of the data-gradient operand, and
+# whether the operands hold padding no pack writes (zeroed once, so that two packs compare equal)
+_Form = collections.namedtuple('_Form', 'name kind dtype n_fwd n_dgrad zero_pad')
+
+
+def _weight_forms(rt, n, dtype):
+    """the forms of the n-element [tap][n][k] operand of `rt` that spec and dtype alone decide"""
+    s, f32 = rt.spec, torch.float32
+    if dtype != f32:
+        return [_Form('gemm', _lib.PACK_GEMM_16[Fn.DT[dtype]], dtype, n, n, False)]
+    if not rt.wino:
+        return [_Form('gemm', _lib.PACK_GEMM, f32, n, n, False)]
+    fs = [_Form('wino', _lib.PACK_WINO, f32, n * 4 // 3, n * 4 // 3, False)]       # U: 4 comps per 3 taps
+    if rt.wino2d:
+        # (the K-step padding of a channel count that is no multiple of 8 is never written)
+        fs.append(_Form('wino2d', _lib.PACK_WINO2D, f32, Fn.wino2d_numel(s.cout, s.cin),
+                        Fn.wino2d_numel(s.cin, s.cout), bool(s.cin % 8 or s.cout % 8)))
+    return fs
+
+
 class ConvRT:
     """nn.Conv2d used as a parameter container + cached packed weights.  fp32 activations run on
     the fp32 kernels (Winograd where eligible); 16-bit activations on conv_h.hip with the weights
@@ -118,17 +140,26 @@ class ConvRT:
         self.spec = Fn.ConvSpec(conv.in_channels, conv.out_channels, tuple(conv.kernel_size),
                                 tuple(conv.stride), tuple(conv.padding))
         # stride-1 3x1 / 1x3 convs run on the Winograd F(2,3) kernel (EMSA_WINO=0 disables it)
-        self.wino = Fn.wino_eligible(self.spec) and os.environ.get('EMSA_WINO', '1') != '0'
+        self.wino = Fn.wino_enabled(self.spec)
         # dense 3x3 convs the per-shape rule sends to the 2-D Winograd F(2x2,3x3) kernel hold its
         # weights U2 as well; the row form stays (fallback for what that kernel refuses)
         self.wino2d = self.wino and Fn.wino2d_selected(self.spec)
         # stride-1 3x1 / 1x3 convs with 64..512 channels in 16-bit storage: the register-stationary
         # streaming kernel (conv_rs.hip) with fragment-ordered weights, where it takes the geometry
         self.rs = Fn.rs_eligible(self.spec)
-        # forms: 'gemm' [tap][n][k] (fp32 and 16-bit), 'wino' U, 'wino2d' U2 (fp32), 'frag'
-        # fragment-ordered (16-bit)
-        self.packs = _PackCache()
+        self.packs = _PackCache()     # the forms of `forms`
         self.plain_asked = 0      # times the [tap][n][k] 16-bit operand of an rs conv was read (PackPlan)
+
+    def forms(self, dtype):
+        """the forms this conv keeps for activations of `dtype`, the operand every kernel takes first:
+        'gemm' [tap][n][k] (16-bit, and fp32 without the Winograd form) or 'wino' U (fp32); then
+        'frag' fragment-ordered (16-bit, conv_rs) or 'wino2d' U2 (fp32, per-shape rule).  What
+        `_operands` reads and PackPlan packs; decided per call (tests flip Fn.CONV_RS)"""
+        n = self.conv.weight.numel()
+        fs = _weight_forms(self, n, dtype)
+        if dtype != torch.float32 and self.rs and Fn.CONV_RS:
+            fs.append(_Form('frag', _lib.PACK_FRAG_16[Fn.DT[dtype]], dtype, n, n, False))
+        return fs
 
     def spec_key(self):
         s = self.spec
@@ -160,17 +191,28 @@ class ConvRT:
         return self.packs.get(form, dtype, side, (w._version, w.data_ptr()),
                               lambda fwd, dgrad: self._pack(form, dtype, fwd, dgrad), w.requires_grad)
 
+    def _operands(self, side, dtype, wino2d=True):
+        """(wp, keyword arguments) of Fn.conv_fwd (side 0) / Fn.conv_dgrad (side 1) that hand over
+        this conv's operands for activations of `dtype`, best kernel first; wino2d=False: without U2"""
+        if dtype != torch.float32:
+            wf = self.frag(dtype, side)
+            if wf is None:
+                return self.packed(dtype, side), {}
+            # the [tap][n][k] operand of a conv_rs-capable conv ON DEMAND: where conv_rs takes the
+            # geometry (every NBt1D conv of a training step) nobody reads it, and PackPlan stops
+            # packing it (`plain_asked` tells it when somebody did)
+            return (lambda: self.packed(dtype, side)), {'wfrag': wf}
+        if self.wino2d and wino2d:
+            return None, {'wino2d_u': self.weights('wino2d', side),
+                          'wino_u': lambda: self.weights('wino', side)}
+        if self.wino:
+            return None, {'wino_u': self.weights('wino', side)}
+        return self.packed(side=side), {}
+
     def forward(self, x, **kw):
         """conv forward through the best kernel for this layer (fused-epilogue kwargs of conv_fwd)"""
-        if x.dtype != torch.float32:
-            wf = self.frag(x.dtype)
-            return Fn.conv_fwd(x, self._plain(x.dtype, wf, self.packed), self.spec, wfrag=wf, **kw)
-        if self.wino2d:
-            return Fn.conv_fwd(x, None, self.spec, wino2d_u=self.weights('wino2d', 0),
-                               wino_u=lambda: self.weights('wino', 0), **kw)
-        if self.wino:
-            return Fn.conv_fwd(x, None, self.spec, wino_u=self.weights('wino', 0), **kw)
-        return Fn.conv_fwd(x, self.packed(), self.spec, **kw)
+        wp, operands = self._operands(0, x.dtype)
+        return Fn.conv_fwd(x, wp, self.spec, **operands, **kw)
 
     def folds_input_bn(self, t):
         """this conv can take the BatchNorm + ReLU in front of it (input tensor `t`) into its
@@ -182,18 +224,9 @@ class ConvRT:
 
     def dgrad(self, dy, in_hw, mask_bits=None, **kw):
         """mask_bits: the ReLU mask of the producing layer as bits (conv_fwd(want_relu_bits));
-        used by the Winograd kernel, otherwise the float `mask_src` applies"""
-        if dy.dtype != torch.float32:
-            wf = self.frag_dgrad(dy.dtype)
-            return Fn.conv_dgrad(dy, self._plain(dy.dtype, wf, self.packed_dgrad), self.spec, in_hw,
-                                 wfrag=wf, **kw)
-        if self.wino2d and mask_bits is None:
-            return Fn.conv_dgrad(dy, None, self.spec, in_hw, wino2d_u=self.weights('wino2d', 1),
-                                 wino_u=lambda: self.weights('wino', 1), **kw)
-        if self.wino:
-            return Fn.conv_dgrad(dy, None, self.spec, in_hw, wino_u=self.weights('wino', 1),
-                                 mask_bits=mask_bits, **kw)
-        return Fn.conv_dgrad(dy, self.packed_dgrad(), self.spec, in_hw, **kw)
+        used by the 1-D Winograd kernel (U2 stays out then), otherwise the float `mask_src` applies"""
+        wp, operands = self._operands(1, dy.dtype, wino2d=mask_bits is None)
+        return Fn.conv_dgrad(dy, wp, self.spec, in_hw, mask_bits=mask_bits, **operands, **kw)
 
     def dgrad_takes_res_bits(self, dy, in_hw, residual):
         """this conv's data gradient can mask its residual operand by bits (Fn.conv_dgrad res_bits):
@@ -207,53 +240,51 @@ class ConvRT:
         into this conv's loader: no ReLU bit mask exists)"""
         if affine is None or not (force or Fn.bn_fused_reduce(dy.dtype, self.spec.cin)):
             return None
-        scale, shift = affine
-        if dy.dtype != torch.float32:
-            wf = self.frag_dgrad(dy.dtype)
-            return Fn.conv_dgrad_bnb(dy, self._plain(dy.dtype, wf, self.packed_dgrad), self.spec, in_hw,
-                                     t, scale, shift, mean, invstd, residual=residual, wfrag=wf)
-        if not self.wino:
+        if dy.dtype == torch.float32 and not self.wino:
             return None
-        return Fn.conv_dgrad_bnb(dy, None, self.spec, in_hw, t, scale, shift, mean, invstd,
-                                 residual=residual, wino_u=self.weights('wino', 1))
-
-    def _plain(self, dtype, wfrag, getter):
-        """the [tap][n][k] operand of the implicit GEMM: at once for a conv without fragment-ordered
-        weights, ON DEMAND for a conv_rs-capable one -- where conv_rs takes the geometry (every NBt1D
-        conv of a training step) nobody reads it, and PackPlan stops packing it (`plain_asked`
-        tells it when somebody did)"""
-        if wfrag is None:
-            return getter(dtype)
-
-        return lambda: getter(dtype)
+        scale, shift = affine
+        wp, operands = self._operands(1, dy.dtype, wino2d=False)
+        return Fn.conv_dgrad_bnb(dy, wp, self.spec, in_hw, t, scale, shift, mean, invstd,
+                                 residual=residual, **operands)
 
     def frag(self, dtype, side=0):
         """fragment-ordered weights for conv_rs.hip (None: not that kind of conv)"""
         return self.weights('frag', side, dtype) if self.rs and Fn.CONV_RS else None
-
-    def frag_dgrad(self, dtype):
-        return self.frag(dtype, 1)
 
     def packed(self, dtype=torch.float32, side=0):
         if dtype != torch.float32:
             self.plain_asked += 1
         return self.weights('gemm', side, dtype)
 
-    def packed_dgrad(self, dtype=torch.float32):
-        return self.packed(dtype, 1)
-
 
 # EMSA_PACK_LEAN=0: always pack both 16-bit operand forms of the conv_rs-capable convs (A/B runs)
 PACK_LEAN = os.environ.get('EMSA_PACK_LEAN', '1') != '0'
+
+# One job of PackPlan's table before it has addresses: `owner` (ConvRT / MultiConvRT) gets `form`
+# (a _Form; None: the empty job a lean table keeps in a skipped operand's place) packed from the
+# parameter `src` by a job of `kind` with dims = (cout, cin, kh, kw) and place = (cout_total, cout_off,
+# cin_total, cin_off) inside a wider operand; elems = elements of the (forward, data-gradient) side, 0:
+# no such side; persistent: into the owner's zero-initialised operand of that form, which all its
+# placements share (merged heads), instead of into views carved from the arena
+_PackEntry = collections.namedtuple('_PackEntry', 'owner form src kind dims place elems persistent')
+
+# What one `PackPlan._build` made, and what a captured launch holds raw pointers into: the job table
+# on the device, its launch arguments, the arena, views = {(owner, form): (fwd, dgrad)} -- arena views
+# and the merged heads' operands -- and what it was built for: dtype, the parameters' addresses, and
+# per conv whether its first form has a data-gradient side (None: skipped by a lean table)
+_PackBuild = collections.namedtuple('_PackBuild', 'jobs n_jobs n_blocks arena views dtype ptrs two_sided')
 
 
 class PackPlan:
     """All weight transforms of a model (packed implicit-GEMM layouts, Winograd U, or the 16-bit
     operands of the mixed-precision path) in ONE launch per optimizer step instead of one ~5 us
     kernel per layer (380 launches = 2.3 ms per step).  `refresh(dtype)` (called at the start of
-    the model's forward) re-packs every registered ConvRT when any weight changed and installs the
-    results in the ConvRTs' own caches (`_PackCache.put`), so their per-layer fallback
-    (`weights()`) finds fresh entries and launches nothing."""
+    the model's forward) re-packs every form of `forms(dtype)` of every registered runtime when any
+    weight changed and installs the results in the runtimes' own caches (`_PackCache.put`), so their
+    per-layer fallback (`weights()`) finds fresh entries and launches nothing."""
+
+    # forms whose jobs come after every conv's first form in the table
+    _SECOND = ('frag', 'wino2d')
 
     def __init__(self, rts):
         self.rts = [rt for rt in rts if isinstance(rt, ConvRT)]
@@ -261,14 +292,8 @@ class PackPlan:
         # job per placed parameter (+ one per bias) into persistent zero-initialised operands --
         # they used to re-pack themselves every step with a zero-fill and 2-4 kernels each
         self.multi = [rt for rt in rts if isinstance(rt, MultiConvRT)]
-        self._mviews = None
         self._key = None
-        self._ptrs = None
-        self._jobs = None
-        self._n_blocks = 0
-        self._arena = None
-        self._views = None
-        self._dtype = None
+        self._built = None            # _PackBuild
         # lean: the conv_rs-capable convs get their fragment-ordered 16-bit operands only -- their
         # [tap][n][k] form (half of the 16-bit pack launch: 188 convs of the full model) is read only
         # where conv_rs refuses a geometry.  Decided from what the previous step asked for
@@ -276,7 +301,6 @@ class PackPlan:
         # full again as soon as one turns up (who meanwhile packs per layer, ConvRT.packed)
         self._lean = False
         self._asked_seen = None
-        self._refreshes = 0
         # a hipGraph that captured `emsa_pack_batch` holds RAW pointers to the job table, the arena
         # and the merged-head operands.  Once a refresh ran under capture the lean / full state is
         # frozen (the table a replay reads must stay the one it recorded) and whatever a later
@@ -284,7 +308,10 @@ class PackPlan:
         # going back to the allocator, where a replay would scribble over someone else's memory
         # (ADVICE r5).  `thaw()` drops both when the graphs are gone.
         self._captured = False
-        self._retired = []
+        self._retired = []            # superseded _PackBuilds
+
+    _jobs = property(lambda self: self._built and self._built.jobs)
+    _arena = property(lambda self: self._built and self._built.arena)
 
     def thaw(self):
         """no captured graph replays this plan's pack launch any more: allow lean / full switches
@@ -295,157 +322,105 @@ class PackPlan:
     def _asked(self):
         return sum(rt.plain_asked for rt in self.rts if rt.rs)
 
-    def _build(self, dev, dtype, lean=False):
-        if self._captured and self._jobs is not None:
-            self._retired.append((self._jobs, self._arena, self._views, self._frag, self._mviews,
-                                  self._w2))
-        self._lean = lean
-        n = len(self.rts)
-        n_multi = sum(len(m.placements) + sum(1 for q, _, _ in m.placements if q.bias is not None)
-                      for m in self.multi)
-        half = dtype != torch.float32
-        # the stride-1 3-tap 1-D convs additionally get the fragment-ordered operands of conv_rs.hip
-        # (pack kinds 5 / 6) -- the [tap][n][k] form stays for geometries that kernel refuses
-        frag_rts = [rt for rt in self.rts if half and rt.rs and Fn.CONV_RS]
-        lean = self._lean = bool(lean and frag_rts)
-        skip = set(id(rt) for rt in frag_rts) if lean else set()
-        # the dense 3x3 convs on the 2-D Winograd kernel get U2 (pack kind 7) BESIDE their row form
-        w2_rts = [rt for rt in self.rts if not half and rt.wino2d]
-        n_multi2 = sum(len(m.placements) for m in self.multi if m.wino2d and not half)
-        jobs = (_lib.EmsaPackJob * (n + n_multi + len(frag_rts) + len(w2_rts) + n_multi2))()
-        esz = 2 if half else 4
-        sizes = []
-        for rt in self.rts:
-            w = rt.conv.weight
-            numel = w.numel()
-            per = numel if half else (numel * 4 // 3 if rt.wino else numel)   # U: 4 comps per 3 taps
-            per_b = (per * esz + 15) // 16 * 16            # every pack starts 16-byte aligned
-            if id(rt) in skip:
-                sizes.append((0, 0, 0))
-            else:
-                sizes.append((per, per_b, per_b if w.requires_grad else 0))
-        fsizes = [((rt.conv.weight.numel() * esz + 15) // 16 * 16) * (2 if rt.conv.weight.requires_grad else 1)
-                  for rt in frag_rts]
-        # (U2 forward and data gradient have the same size when both channel counts are multiples of
-        # 8, which the per-shape rule's convs are; otherwise the larger of the two)
-        w2numel = [max(Fn.wino2d_numel(rt.spec.cout, rt.spec.cin),
-                       Fn.wino2d_numel(rt.spec.cin, rt.spec.cout)) for rt in w2_rts]
-        w2sizes = [nel * 4 * (2 if rt.conv.weight.requires_grad else 1)
-                   for rt, nel in zip(w2_rts, w2numel)]
-        arena = Fn._empty((sum(a + b for _, a, b in sizes) + sum(fsizes) + sum(w2sizes),), dev,
-                          torch.uint8)
-        views, off, blk = [], 0, 0
-        for j, (rt, (per, a, b)) in enumerate(zip(self.rts, sizes)):
-            w = rt.conv.weight
-            if id(rt) in skip:
-                # lean: no [tap][n][k] operand for this conv -- an empty job keeps the table's indexing
-                views.append((None, None))
-                jobs[j] = _lib.EmsaPackJob(w.data_ptr(), w.data_ptr(), None, 0, 1, 1, 1, 4, blk)
-                blk += 1
-                continue
-            v0 = arena[off:off + per * esz].view(dtype)
-            v1 = arena[off + a:off + a + per * esz].view(dtype) if b else None
-            off += a + b
-            views.append((v0, v1))
-            cout, cin, kh, kw = w.shape
-            kind = Fn.DT[dtype] + 1 if half else (1 if rt.wino else 0)   # 2 = bf16, 3 = fp16
-            jobs[j] = _lib.EmsaPackJob(w.data_ptr(), v0.data_ptr(), v1.data_ptr() if b else None,
-                                       cout, cin, kh, kw, kind, blk)
-            blk += max(1, min(64, (w.numel() + 2047) // 2048))
-        j = n
-        fviews = []
-        for rt, fs in zip(frag_rts, fsizes):
-            w = rt.conv.weight
-            nb = w.numel() * esz
-            one = fs // 2 if w.requires_grad else fs
-            f0 = arena[off:off + nb].view(dtype)
-            f1 = arena[off + one:off + one + nb].view(dtype) if w.requires_grad else None
-            off += fs
-            fviews.append((f0, f1))
-            cout, cin, kh, kw = w.shape
-            jobs[j] = _lib.EmsaPackJob(w.data_ptr(), f0.data_ptr(),
-                                       f1.data_ptr() if f1 is not None else None, cout, cin, kh, kw,
-                                       Fn.DT[dtype] + 4, blk)            # 5 = bf16, 6 = fp16
-            blk += max(1, min(64, (w.numel() + 2047) // 2048))
-            j += 1
-        self._frag = (frag_rts, fviews)
-        w2views = []
-        for rt, fs in zip(w2_rts, w2sizes):
-            w = rt.conv.weight
-            one = fs // 2 if w.requires_grad else fs
-            u0 = arena[off:off + 4 * Fn.wino2d_numel(rt.spec.cout, rt.spec.cin)].view(torch.float32)
-            u1 = arena[off + one:off + one + 4 * Fn.wino2d_numel(rt.spec.cin, rt.spec.cout)] \
-                .view(torch.float32) if w.requires_grad else None
-            if rt.spec.cin % 8 or rt.spec.cout % 8:
-                arena[off:off + fs].zero_()        # the K-step padding, never read by the kernel
-            off += fs
-            w2views.append((u0, u1))
-            cout, cin, kh, kw = w.shape
-            jobs[j] = _lib.EmsaPackJob(w.data_ptr(), u0.data_ptr(),
-                                       u1.data_ptr() if u1 is not None else None, cout, cin, kh, kw,
-                                       7, blk)
-            blk += max(1, min(64, (w.numel() + 2047) // 2048))
-            j += 1
-        self._w2 = (w2_rts, w2views)
-        mviews = []
+    def _src_ptrs(self):
+        return tuple(rt.conv.weight.data_ptr() for rt in self.rts) + \
+            tuple(q.weight.data_ptr() for m in self.multi for q, _, _ in m.placements)
+
+    def _entries(self, dtype, lean):
+        """the table in its order: every conv's first form, then the convs' second forms; then head by
+        head the first form and the bias placement by placement, then the head's second form.  lean:
+        a conv with fragment-ordered weights gets an empty job (one block) for its [tap][n][k] form"""
+        ents = []
+        for second in (False, True):
+            for rt in self.rts:
+                w, forms = rt.conv.weight, rt.forms(dtype)
+                skip = lean and any(f.name == 'frag' for f in forms)
+                for f in forms:
+                    if (f.name in self._SECOND) != second:
+                        continue
+                    if skip and f.name == 'gemm':
+                        ents.append(_PackEntry(rt, None, w, _lib.PACK_COPY, (0, 1, 1, 1), (0, 0, 0, 0),
+                                               (0, 0), False))
+                    else:
+                        ents.append(_PackEntry(rt, f, w, f.kind, tuple(w.shape), (0, 0, 0, 0),
+                                               (f.n_fwd, f.n_dgrad if w.requires_grad else 0), False))
         for m in self.multi:
-            sp = m.spec
-            taps = sp.kh * sp.kw
-            wino = m.wino and not half
-            numel = taps * sp.cout * sp.cin
-            per = numel * 4 // 3 if wino else numel
-            d0 = Fn._zeros((per,), dev, dtype)          # forward operand / Winograd U
-            d1 = Fn._zeros((per,), dev, dtype)          # data-gradient operand / U
-            bias = Fn._zeros((sp.cout,), dev) if m.has_bias else None
-            kind = Fn.DT[dtype] + 1 if half else (1 if wino else 0)
-            for q, co, ci in m.placements:
-                w4 = m._w4(q)
-                cout, cin, kh, kw = w4.shape
-                jobs[j] = _lib.EmsaPackJob(q.weight.data_ptr(), d0.data_ptr(), d1.data_ptr(), cout,
-                                           cin, kh, kw, kind, blk, sp.cout, co, sp.cin, ci)
-                blk += max(1, min(64, (w4.numel() + 2047) // 2048))
-                j += 1
-                if q.bias is not None:
-                    jobs[j] = _lib.EmsaPackJob(q.bias.data_ptr(), bias.data_ptr(), None,
-                                               q.bias.shape[0], 1, 1, 1, 4, blk, sp.cout, co, 1, 0)
-                    blk += 1
-                    j += 1
-            d2 = d3 = None
-            if wino and m.wino2d:
-                d2 = Fn._zeros((Fn.wino2d_numel(sp.cout, sp.cin),), dev, dtype)   # U2 forward
-                d3 = Fn._zeros((Fn.wino2d_numel(sp.cin, sp.cout),), dev, dtype)   # data gradient
+            s = m.spec
+            for second in (False, True):
                 for q, co, ci in m.placements:
-                    w4 = m._w4(q)
-                    cout, cin, kh, kw = w4.shape
-                    jobs[j] = _lib.EmsaPackJob(q.weight.data_ptr(), d2.data_ptr(), d3.data_ptr(), cout,
-                                               cin, kh, kw, 7, blk, sp.cout, co, sp.cin, ci)
-                    blk += max(1, min(64, (w4.numel() + 2047) // 2048))
-                    j += 1
-            mviews.append((d0, d1, bias, wino, d2, d3))
-        self._mviews = mviews
-        self._n_jobs = j
+                    for f in m.forms(dtype):
+                        if f.kind is None or (f.name in self._SECOND) != second:
+                            continue
+                        if f.name != 'bias':
+                            ents.append(_PackEntry(m, f, q.weight, f.kind, tuple(m._w4(q).shape),
+                                                   (s.cout, co, s.cin, ci), (f.n_fwd, f.n_dgrad), True))
+                        elif q.bias is not None:
+                            ents.append(_PackEntry(m, f, q.bias, f.kind, (q.bias.shape[0], 1, 1, 1),
+                                                   (s.cout, co, 1, 0), (f.n_fwd, 0), True))
+        return ents
+
+    @staticmethod
+    def _span(e):
+        """(bytes of one side, sides) an entry takes of the arena: every pack starts 16-byte aligned,
+        the data-gradient side one side's bytes behind the forward side"""
+        if e.form is None or e.persistent:
+            return 0, 0
+        return (max(e.elems) * e.form.dtype.itemsize + 15) // 16 * 16, 2 if e.elems[1] else 1
+
+    def _build(self, dev, dtype, lean=False):
+        if self._captured and self._built is not None:
+            self._retired.append(self._built)
+        ents = self._entries(dtype, lean)
+        self._lean = any(e.form is None for e in ents)
+        arena = Fn._empty((sum(nb * sides for nb, sides in map(self._span, ents)),), dev, torch.uint8)
+        jobs = (_lib.EmsaPackJob * len(ents))()
+        views, off, blk = {}, 0, 0
+        for j, e in enumerate(ents):
+            key, (n_fwd, n_dgrad) = (e.owner, e.form), e.elems
+            if e.form is None:
+                # lean: no [tap][n][k] operand for this conv -- an empty job keeps the table's indexing
+                fwd, dgrad = e.src, None
+            elif e.persistent:
+                if key not in views:
+                    views[key] = (Fn._zeros((n_fwd,), dev, e.form.dtype),
+                                  Fn._zeros((n_dgrad,), dev, e.form.dtype) if n_dgrad else None)
+                fwd, dgrad = views[key]
+            else:
+                (nb, sides), dt = self._span(e), e.form.dtype
+                if e.form.zero_pad:
+                    arena[off:off + nb * sides].zero_()        # the K-step padding, never read by the kernel
+                fwd = arena[off:off + n_fwd * dt.itemsize].view(dt)
+                dgrad = arena[off + nb:off + nb + n_dgrad * dt.itemsize].view(dt) if n_dgrad else None
+                off += nb * sides
+                views[key] = (fwd, dgrad)
+            jobs[j] = _lib.EmsaPackJob(e.src.data_ptr(), fwd.data_ptr(),
+                                       dgrad.data_ptr() if dgrad is not None else None, *e.dims,
+                                       e.kind, blk, *e.place)
+            cout, cin, kh, kw = e.dims
+            blk += max(1, min(64, (cout * cin * kh * kw + 2047) // 2048))
         raw = torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8).to(dev)
-        self._jobs, self._n_blocks, self._arena, self._views = raw, blk, arena, views
-        self._mptrs = tuple(q.weight.data_ptr() for m in self.multi for q, _, _ in m.placements)
-        self._ptrs = tuple(rt.conv.weight.data_ptr() for rt in self.rts)
-        self._dtype = dtype
+        two_sided = tuple(None if e.form is None else e.elems[1] > 0 for e in ents[:len(self.rts)])
+        self._built = _PackBuild(raw, len(ents), blk, arena, views, dtype, self._src_ptrs(), two_sided)
+
+    def _install(self):
+        """the install step of `refresh`: every view of the current table into its owner's cache (a
+        lean table has none for a skipped operand: ConvRT.packed packs that one itself if asked)"""
+        for (owner, form), (fwd, dgrad) in self._built.views.items():
+            owner.packs.put(form.name, form.dtype, owner.key_now(), fwd, dgrad)
 
     def refresh(self, dtype=torch.float32):
         if not self.rts:
             return
         ws = [rt.conv.weight for rt in self.rts]
-        mkeys = [m.key_now() for m in self.multi]
         key = (dtype,) + tuple((w._version, w.data_ptr(), w.requires_grad) for w in ws) + \
-            tuple(mkeys)
+            tuple(m.key_now() for m in self.multi)
         if key == self._key:
             return
         if not ws[0].is_cuda:
             return                                   # host-side dry runs: per-layer path
-        mptrs = tuple(q.weight.data_ptr() for m in self.multi for q, _, _ in m.placements)
-        if self._dtype != dtype or self._ptrs != tuple(w.data_ptr() for w in ws) or \
-                getattr(self, '_mptrs', None) != mptrs or \
-                any(v0 is not None and (v1 is None) == w.requires_grad
-                    for (v0, v1), w in zip(self._views or [], ws)):
+        b = self._built
+        if b is None or b.dtype != dtype or b.ptrs != self._src_ptrs() or \
+                any(t is not None and t != w.requires_grad for t, w in zip(b.two_sided, ws)):
             self._build(ws[0].device, dtype, self._lean)
         # lean / full job table, from what the step behind us read (never switched inside a capture:
         # _build uploads the table)
@@ -458,23 +433,10 @@ class PackPlan:
             elif not self._lean and self._asked_seen is not None and asked == self._asked_seen:
                 self._build(ws[0].device, dtype, True)
         self._asked_seen = asked
-        check(_lib.lib().emsa_pack_batch(self._jobs.data_ptr(), self._n_jobs, self._n_blocks,
-                                         Fn._stream()), 'emsa_pack_batch')
-        for m, mk, (d0, d1, bias, wino, d2, d3) in zip(self.multi, mkeys, self._mviews):
-            # (an fp32 Winograd head gets U and the bias, no GEMM operand)
-            m.packs.put('wino' if wino else 'gemm', dtype, mk, d0, d1)
-            m.packs.put('bias', torch.float32, mk, bias, None)
-            if d2 is not None:
-                m.packs.put('wino2d', dtype, mk, d2, d3)
-        for rt, (f0, f1) in zip(*self._frag):
-            rt.packs.put('frag', dtype, rt.key_now(), f0, f1)
-        for rt, (u0, u1) in zip(*self._w2):
-            rt.packs.put('wino2d', dtype, rt.key_now(), u0, u1)
-        for rt, (v0, v1) in zip(self.rts, self._views):
-            if v0 is None:
-                continue                       # lean: ConvRT.packed packs this one itself if asked
-            rt.packs.put('wino' if rt.wino and dtype == torch.float32 else 'gemm', dtype,
-                         rt.key_now(), v0, v1)
+        b = self._built
+        check(_lib.lib().emsa_pack_batch(b.jobs.data_ptr(), b.n_jobs, b.n_blocks, Fn._stream()),
+              'emsa_pack_batch')
+        self._install()
         self._key = key
 
 
@@ -1123,12 +1085,24 @@ class MultiConvRT:
         self.spec = Fn.ConvSpec(cin_total, cout_total, kernel, 1, padding)
         self.has_bias = any(m.bias is not None for m, _, _ in placements)
         # 3x3 stride-1 merged convs (the task heads) run on the Winograd kernel as well
-        self.wino = Fn.wino_eligible(self.spec) and os.environ.get('EMSA_WINO', '1') != '0'
+        self.wino = Fn.wino_enabled(self.spec)
         # merged 3x3 heads the per-shape rule sends to the 2-D Winograd kernel: U2 beside the row form
         self.wino2d = self.wino and Fn.wino2d_selected(self.spec)
-        # forms: 'gemm' the assembled [tap][n][k] operands (fp32 and 16-bit), 'wino' U and 'wino2d'
-        # U2 made from them (fp32), 'bias' the assembled fp32 bias vector (forward side only)
-        self.packs = _PackCache()
+        self.packs = _PackCache()     # the forms of `forms`
+
+    def forms(self, dtype):
+        """the forms this conv keeps for activations of `dtype`: 'gemm' the assembled [tap][n][k]
+        operands (16-bit, and fp32 without the Winograd form) or 'wino' U and, per-shape rule, 'wino2d'
+        U2 (fp32); 'bias' the assembled fp32 bias vector (forward side only).  A Winograd head that
+        packs by itself makes U and U2 from its fp32 'gemm' operands: a form no job of PackPlan makes"""
+        s = self.spec
+        n = s.kh * s.kw * s.cout * s.cin
+        fs = _weight_forms(self, n, dtype)
+        if fs[0].name == 'wino':
+            fs.insert(0, _Form('gemm', None, torch.float32, n, n, False))
+        if self.has_bias:
+            fs.append(_Form('bias', _lib.PACK_COPY, torch.float32, s.cout, 0, False))
+        return fs
 
     def _w4(self, m):
         w = m.weight
@@ -1146,30 +1120,19 @@ class MultiConvRT:
                 bias[co:co + m.bias.shape[0]].copy_(m.bias.detach())
         return bias
 
-    # the assembled operands start as zeros: the padding channels and whatever lies between the
-    # placements belong to no parameter, and the kernels read them like any other weight
-    def _assemble_fwd(self, dtype):
-        """forward operand [tap][cout][cin], fp32 or 16-bit"""
+    def _assemble(self, side, dtype):
+        """forward [tap][cout][cin] (side 0) / data-gradient [tap][cin][cout] (side 1) operand, fp32 or
+        16-bit.  It starts as zeros: the padding channels and whatever lies between the placements
+        belong to no parameter, and the kernels read them like any other weight"""
         s = self.spec
         wp = Fn._zeros((s.kh * s.kw * s.cout * s.cin,), self.placements[0][0].weight.device, dtype)
         for m, co, ci in self.placements:
             if dtype == torch.float32:
-                Fn.pack_weight(self._w4(m).detach(), 'fwd', s.cout, co, s.cin, ci, out=wp)
+                Fn.pack_weight(self._w4(m).detach(), 'dgrad' if side else 'fwd', s.cout, co, s.cin, ci,
+                               out=wp)
             else:
-                Fn.pack_weight_t(self._w4(m).detach(), dtype, True, False, s.cout, co, s.cin, ci,
-                                 out_fwd=wp)
-        return wp
-
-    def _assemble_dgrad(self, dtype):
-        """data-gradient operand [tap][cin][cout], fp32 or 16-bit"""
-        s = self.spec
-        wp = Fn._zeros((s.kh * s.kw * s.cout * s.cin,), self.placements[0][0].weight.device, dtype)
-        for m, co, ci in self.placements:
-            if dtype == torch.float32:
-                Fn.pack_weight(self._w4(m).detach(), 'dgrad', s.cout, co, s.cin, ci, out=wp)
-            else:
-                Fn.pack_weight_t(self._w4(m).detach(), dtype, False, True, s.cout, co, s.cin, ci,
-                                 out_dgrad=wp)
+                Fn.pack_weight_t(self._w4(m).detach(), dtype, not side, bool(side), s.cout, co, s.cin, ci,
+                                 out_fwd=None if side else wp, out_dgrad=wp if side else None)
         return wp
 
     def _pack(self, form, dtype, fwd, dgrad):
@@ -1177,8 +1140,8 @@ class MultiConvRT:
         if form == 'bias':
             return self._bias_vec(), None
         if form == 'gemm':
-            return (self._assemble_fwd(dtype) if fwd else None,
-                    self._assemble_dgrad(dtype) if dgrad else None)
+            return (self._assemble(0, dtype) if fwd else None,
+                    self._assemble(1, dtype) if dgrad else None)
         # U / U2 from the CACHED assembled operands: one assembly serves both
         if form == 'wino':
             rows = Fn.wino_rows(s)
@@ -1198,15 +1161,21 @@ class MultiConvRT:
         return self.packs.get(form, dtype, side, self.key_now(),
                               lambda fwd, dgrad: self._pack(form, dtype, fwd, dgrad), False)
 
+    def _operands(self, side, dtype):
+        """(wp, keyword arguments) of Fn.conv_fwd (side 0) / Fn.conv_dgrad (side 1) that hand over
+        this conv's operands for activations of `dtype`"""
+        if dtype != torch.float32 or not self.wino:
+            return self.weights('gemm', side, dtype), {}
+        operands = {'wino_u': self.weights('wino', side)}
+        if self.wino2d:
+            operands['wino2d_u'] = self.weights('wino2d', side)
+        return None, operands
+
     def forward(self, x):
         Fn.prof_flops(self.real_flops(x))
         bias = self.weights('bias', 0) if self.has_bias else None
-        if x.dtype != torch.float32 or not self.wino:
-            return Fn.conv_fwd(x, self.weights('gemm', 0, x.dtype), self.spec, bias=bias)
-        if self.wino2d:
-            return Fn.conv_fwd(x, None, self.spec, bias=bias, wino_u=self.weights('wino', 0),
-                               wino2d_u=self.weights('wino2d', 0))
-        return Fn.conv_fwd(x, None, self.spec, bias=bias, wino_u=self.weights('wino', 0))
+        wp, operands = self._operands(0, x.dtype)
+        return Fn.conv_fwd(x, wp, self.spec, bias=bias, **operands)
 
     def real_flops(self, x):
         """direct-convolution FLOPs of the REAL (un-padded, un-merged) convolutions on `x`"""
@@ -1215,12 +1184,8 @@ class MultiConvRT:
 
     def dgrad(self, dy, in_hw):
         Fn.prof_flops(self.real_flops(dy))
-        if dy.dtype != torch.float32 or not self.wino:
-            return Fn.conv_dgrad(dy, self.weights('gemm', 1, dy.dtype), self.spec, in_hw)
-        if self.wino2d:
-            return Fn.conv_dgrad(dy, None, self.spec, in_hw, wino_u=self.weights('wino', 1),
-                                 wino2d_u=self.weights('wino2d', 1))
-        return Fn.conv_dgrad(dy, None, self.spec, in_hw, wino_u=self.weights('wino', 1))
+        wp, operands = self._operands(1, dy.dtype)
+        return Fn.conv_dgrad(dy, wp, self.spec, in_hw, **operands)
 
     def params(self):
         ps = []

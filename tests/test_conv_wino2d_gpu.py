@@ -255,9 +255,9 @@ def test_wino2d_full_model_train_step(monkeypatch):
         s = m.spec
         got_u2, got_ud2 = m.packs.peek('wino2d', torch.float32, m.key_now())
         assert got_u2 is not None and got_ud2 is not None
-        assert torch.equal(got_u2, Fn.pack_wino2d_packed(m._assemble_fwd(torch.float32), s.cout, s.cin,
+        assert torch.equal(got_u2, Fn.pack_wino2d_packed(m._assemble(0, torch.float32), s.cout, s.cin,
                                                          flip=False))
-        assert torch.equal(got_ud2, Fn.pack_wino2d_packed(m._assemble_dgrad(torch.float32), s.cin, s.cout,
+        assert torch.equal(got_ud2, Fn.pack_wino2d_packed(m._assemble(1, torch.float32), s.cin, s.cout,
                                                           flip=True))
     f32, f64, fo = T._flatten(r32), T._flatten(r64), T._flatten(out)
     assert len(f32) == len(fo) == len(f64)

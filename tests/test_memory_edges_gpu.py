@@ -402,8 +402,8 @@ def test_wgrad_multi_has_no_fp32_or_fp16_form(cfg, dtype, guard_allocations):
                                            (3, BF16, False)])
 def test_merged_head_repack_paths(k, dtype, wino2d, monkeypatch, guard_allocations):
     """ops.MultiConvRT without a PackPlan in front of it: the operand of two convs (5 + 2 output
-    channels in an 8-wide head) is assembled by its own re-pack paths -- `_assemble_fwd` /
-    `_assemble_dgrad`, in the activations' dtype, into zeroed buffers; U and U2 (2-D Winograd) are
+    channels in an 8-wide head) is assembled by its own re-pack path -- `_assemble`, once per side,
+    in the activations' dtype, into zeroed buffers; U and U2 (2-D Winograd) are
     made from those same two operands -- forward and data gradient against the fp64 convs; the
     padding channel is the zero the buffers started with"""
     from emsanet_amd import ops
@@ -435,15 +435,15 @@ def test_merged_head_repack_paths(k, dtype, wino2d, monkeypatch, guard_allocatio
     dx = rt.dgrad(A.put(to_act(dy).to(dtype)), (h, w))
     close(dx, xd.grad, tol=tol, what='merged head dgrad')
     sites = [(e[3].rsplit(':', 1)[0], e[5]) for e in A._live]
-    want = {('ops.py:_assemble_fwd', dtype), ('ops.py:_assemble_dgrad', dtype)}
+    want = {('ops.py:_assemble', dtype)}
     if rt.wino2d:
         # U2 of both sides was made under the guard, from the operands the row form was made from
         want.add(('functional.py:_wino2d_buf', F32))
         assert rt.packs.peek('wino2d', F32, rt.key_now()) != (None, None)
     assert want <= set(sites), (want, sorted(s_ for s_ in sites if s_[0].startswith('ops.py')))
     for site in sorted(want):
-        # each operand is assembled once, whichever forms are made from it
-        assert sites.count(site) == (2 if site[0].startswith('functional.py') else 1), (site, sites)
+        # each operand (forward, data gradient) is assembled once, whichever forms are made from it
+        assert sites.count(site) == 2, (site, sites)
     A.check()
 
 
