@@ -34,7 +34,8 @@ def __getattr__(name):
     if name in ('InferenceOutputPacker', 'write_mapping_output'):
         from . import export
         return getattr(export, name)
-    if name in ('PngEncoder', 'write_scannet_output'):
+    if name in ('PngEncoder', 'write_scannet_output', 'PngDecoder', 'PngFiles', 'PngDecodeError',
+                'png_info'):
         from . import png
         return getattr(png, name)
     raise AttributeError(name)

@@ -217,6 +217,9 @@ SIGNATURES = {
     'emsa_png_bound': (c_int64, [c_int32, c_int32, c_int32]),
     'emsa_png_ws_bytes': (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     'emsa_png_encode': (c_int, [_P, c_int32, c_int32, c_int32, c_int32, _P, c_int64, _P, _P, _P]),
+    'emsa_png_decode_ws_bytes': (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int64]),
+    'emsa_png_decode': (c_int, [_P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, c_int64,
+                                _P]),
     'emsa_targets_workspace_bytes': (c_int64, [c_int32, c_int32, c_int32]),
     'emsa_targets_table_entries': (c_int, [c_int32]),
     'emsa_targets_stats': (c_int, [_P, c_int32, _P, c_int32, _P, c_int32, c_int32, c_int32, c_int32, _TP,

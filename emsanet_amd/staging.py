@@ -19,12 +19,16 @@ generated from the staged maps on the compute stream, under 'targets'.
 With an `augmenter` (`emsanet_amd.augment.TrainingAugmenter`) the loader ships UN-AUGMENTED raw frames
 and label maps: resize, crop, HSV jitter and flip run fused with the normalisation when the batch is
 handed out, and the targets are generated from the augmented maps.
+With a `decoder` (`emsanet_amd.png.PngDecoder`) the loader may ship a value as the PNG FILES themselves
+(`emsanet_amd.png.PngFiles`): only the file bytes cross on the copy stream, and the files are decoded on
+the compute stream when the batch is handed out, in front of everything above.
 """
 from typing import Dict, Iterable, Iterator
 
 import torch
 
 from . import _lib
+from .png import PngFiles
 from .postprocessing import normalize_depth, normalize_rgb
 
 
@@ -39,10 +43,14 @@ class BatchStager:
     augmenter: when given, its `apply` runs over the staged raw buffers instead of the two
     normalisation kernels (it carries its own depth statistics); its outputs -- normalised inputs,
     augmented label maps, orientation table -- are handed out and feed the target generator.  The same
-    holds for the depth of its ring."""
+    holds for the depth of its ring.
+    decoder: when given, a batch value that is a `PngFiles` has its file bytes and offsets table staged
+    (`bytes_staged` counts the file bytes) and is decoded at hand-out into the decoder's own ring; the
+    stack then takes the place of the raw frames.  `decoder.check()` stays the caller's (it synchronises)."""
 
     def __init__(self, host_batches: Iterable[Dict], device, depth_stats=(0.0, 1.0), ring: int = 2,
-                 rgb_key: str = 'rgb', depth_key: str = 'depth', target_generator=None, augmenter=None):
+                 rgb_key: str = 'rgb', depth_key: str = 'depth', target_generator=None, augmenter=None,
+                 decoder=None):
         self.device = torch.device(device)
         if self.device.type != 'cuda':
             raise _lib.EmsaError(f"BatchStager stages batches onto an AMD GPU, not onto {self.device}")
@@ -54,6 +62,7 @@ class BatchStager:
         self.rgb_key, self.depth_key = rgb_key, depth_key
         self.target_generator = target_generator
         self.augmenter = augmenter
+        self.decoder = decoder
         self.copy_stream = torch.cuda.Stream(device=self.device)
         self._slots = [dict(bufs={}, copied=torch.cuda.Event(), freed=None) for _ in range(ring)]
         self.bytes_staged = 0
@@ -61,11 +70,15 @@ class BatchStager:
 
     # -- one slot: raw device buffers that the copy stream fills and the compute stream drains ----
     def _issue(self, slot, host_batch):
+        slot['files'] = {}
         with torch.cuda.stream(self.copy_stream):
             if slot['freed'] is not None:
                 # the buffers' previous content was consumed by kernels on the compute stream
                 self.copy_stream.wait_event(slot['freed'])
             for k, v in host_batch.items():
+                if isinstance(v, PngFiles):
+                    slot['files'][k] = self._issue_files(slot, k, v)
+                    continue
                 if not torch.is_tensor(v):
                     continue
                 if v.is_cuda:
@@ -81,23 +94,51 @@ class BatchStager:
                 buf.copy_(v, non_blocking=True)
                 self.bytes_staged += v.numel() * v.element_size()
             slot['copied'].record(self.copy_stream)
-        slot['extra'] = {k: v for k, v in host_batch.items() if not torch.is_tensor(v)}
-        slot['keys'] = [k for k, v in host_batch.items() if torch.is_tensor(v)]
+        slot['extra'] = {k: v for k, v in host_batch.items() if not (torch.is_tensor(v) or isinstance(v, PngFiles))}
+        slot['keys'] = [k for k, v in host_batch.items() if torch.is_tensor(v) or isinstance(v, PngFiles)]
         self.batches_staged += 1
+
+    def _issue_files(self, slot, k, files):
+        """(on the copy stream) the file bytes and the offsets table of one PngFiles into the slot's byte
+        buffer, which grows in powers of two -> the PngFiles over the device copies"""
+        if self.decoder is None:
+            raise _lib.EmsaError(f"batch['{k}'] is a PngFiles and the stager has no decoder: "
+                                 "BatchStager(..., decoder=PngDecoder())")
+        if files.data.is_cuda:
+            return files
+        if not (files.data.is_pinned() and files.offsets.is_pinned()):
+            raise _lib.EmsaError(f"batch['{k}']: the files are in pageable host memory: the overlapped copy "
+                                 "needs pinned memory (PngFiles.from_bytes pins)")
+        name = ('png', k)
+        buf = slot['bufs'].get(name)
+        n = files.data.numel()
+        if buf is None or buf[0].numel() < n or buf[1].numel() != files.m + 1:
+            size = 1 << max(12, (n - 1).bit_length())
+            buf = slot['bufs'][name] = (torch.empty(size, dtype=torch.uint8, device=self.device),
+                                        torch.empty(files.m + 1, dtype=torch.int64, device=self.device))
+        buf[0][:n].copy_(files.data, non_blocking=True)
+        buf[1].copy_(files.offsets, non_blocking=True)
+        self.bytes_staged += n
+        return PngFiles(buf[0], buf[1], files.m, files.layout, files.h, files.w, files.file_bytes, n)
 
     def _hand_out(self, slot):
         cur = torch.cuda.current_stream(self.device)
         cur.wait_event(slot['copied'])
         out = dict(slot['extra'])
+        bufs = slot['bufs']
+        if slot['files']:
+            # reads the file bytes on the compute stream: covered by the `freed` event below
+            bufs = dict(bufs)
+            bufs.update(self.decoder.decode_batch(slot['files']))
         augmented = {}
         if self.augmenter is not None:
             # reads the raw buffers on the compute stream: covered by the `freed` event below
             names = {self.rgb_key: 'rgb', self.depth_key: 'depth'}
-            res = self.augmenter.apply({names.get(k, k): slot['bufs'][k] for k in slot['keys']})
+            res = self.augmenter.apply({names.get(k, k): bufs[k] for k in slot['keys']})
             back = {'rgb': self.rgb_key, 'depth': self.depth_key}
             augmented = {back.get(k, k): v for k, v in res.items()}
         for k in slot['keys']:
-            raw = slot['bufs'][k]
+            raw = bufs[k]
             if k in augmented:
                 out[k] = augmented[k]
             elif k == self.rgb_key and raw.dtype == torch.uint8:
@@ -110,7 +151,7 @@ class BatchStager:
         if self.target_generator is not None:
             # reads the raw buffers on the compute stream: covered by the `freed` event below
             out['targets'] = self.target_generator.generate(
-                {k: augmented.get(k, slot['bufs'][k]) for k in slot['keys']})
+                {k: augmented.get(k, bufs[k]) for k in slot['keys']})
         ev = torch.cuda.Event()
         ev.record(cur)           # every reader of the raw buffers has been enqueued before this
         slot['freed'] = ev

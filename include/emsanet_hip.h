@@ -1004,6 +1004,58 @@ int emsa_png_encode(const void* src, int32_t layout, int32_t m, int32_t h, int32
                     int64_t data_bytes, int64_t* offsets, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * PNG decoding on the device (csrc/png_decode.hip, csrc/png_inflate_core.h): the training inputs the
+ * reference's datasets store as PNG files -- RGB, depth, semantic and instance maps -- become the dense
+ * stacks BatchStager / TrainingAugmenter read, so that only file bytes cross to the device.
+ * Input: m complete PNG files, contiguous in data[data_bytes] (DEVICE) with offsets int64[m + 1]
+ * (DEVICE): file i is data[offsets[i] : offsets[i + 1]] -- the form emsa_png_encode leaves.  All files
+ * of a call have one layout and size:
+ *     colour type 0, depth 8    EMSA_PNG_GRAY8    dst uint8  [m][h][w]
+ *     colour type 2, depth 8    EMSA_PNG_BGR8     dst uint8  [m][h][w][3], order EMSA_PNGD_RGB (R, G, B
+ *                                                 in memory, as the stager takes it) or EMSA_PNGD_BGR
+ *                                                 (the layout emsa_png_encode reads)
+ *     colour type 0, depth 16   EMSA_PNG_GRAY16   dst uint16 [m][h][w], host byte order
+ * Any deflate stream is read (stored, fixed and dynamic blocks, windows up to 32 KiB, IDAT chunks
+ * split anywhere, ancillary chunks skipped) and all five filter types.  Chunk CRC-32s are NOT
+ * verified; the Adler-32 of the scanlines is.  Palette, alpha, 16-bit RGB, depths below 8 and
+ * interlaced files are to be refused on the host from the IHDR (a file that differs from the call
+ * gets EMSA_PNGD_IHDR).
+ *   emsa_png_decode_ws_bytes   scratch bytes for files of at most file_bytes each (per file: its IDAT
+ *       payloads joined into one zlib stream, and its filtered scanlines h * (1 + w * bpp)).
+ *       EMSA_E_SHAPE for a bad geometry or file_bytes outside [1, 2^30].
+ *   emsa_png_decode   launches only (two kernels: chunk walk + inflate + Adler-32, one wave per file;
+ *       unfilter + output layout, one wave per file): no allocation, copy or synchronisation.
+ *       status int32[m] (DEVICE): EMSA_PNGD_* per file.  A failed file gets an all-zero image; the
+ *       other files of the call are unaffected.  No byte outside data[offsets[i] : offsets[i + 1]] is
+ *       read for file i (offsets outside [0, data_bytes] or not ascending: EMSA_PNGD_CHUNK, nothing
+ *       read), nothing outside dst, status and ws is written, whatever the bytes are.  The per-file
+ *       capacity for the joined stream is ws_bytes / m less the scanlines; a file whose IDAT payloads
+ *       exceed it gets EMSA_PNGD_CHUNK.  ws 16-byte aligned, ws_bytes >= emsa_png_decode_ws_bytes(...,
+ *       16) (EMSA_E_SHAPE otherwise, as for a bad geometry or order).  The output is a pure function
+ *       of the input: no atomics on global memory.
+ * ------------------------------------------------------------------------------------------ */
+#define EMSA_PNGD_RGB 0
+#define EMSA_PNGD_BGR 1
+#define EMSA_PNGD_OK 0
+#define EMSA_PNGD_CHUNK 1         /* bad signature / chunk structure */
+#define EMSA_PNGD_IHDR 2          /* IHDR differs from the call */
+#define EMSA_PNGD_TRUNCATED 3     /* the zlib stream ends early */
+#define EMSA_PNGD_ZLIB_HEADER 4
+#define EMSA_PNGD_BLOCK_TYPE 5
+#define EMSA_PNGD_STORED_LEN 6    /* LEN / NLEN of a stored block disagree */
+#define EMSA_PNGD_CODE_LENGTHS 7  /* over-subscribed or incomplete code */
+#define EMSA_PNGD_SYMBOL 8        /* invalid literal/length or distance code */
+#define EMSA_PNGD_DISTANCE 9      /* distance before the start of the output */
+#define EMSA_PNGD_TOO_MANY 10     /* more than h * (1 + stride) scanline bytes */
+#define EMSA_PNGD_TOO_FEW 11
+#define EMSA_PNGD_FILTER 12       /* filter type above 4 */
+#define EMSA_PNGD_ADLER 13
+int64_t emsa_png_decode_ws_bytes(int32_t layout, int32_t m, int32_t h, int32_t w, int64_t file_bytes);
+int emsa_png_decode(const uint8_t* data, const int64_t* offsets, int64_t data_bytes, int32_t m,
+                    int32_t layout, int32_t order, int32_t h, int32_t w, void* dst, int32_t* status,
+                    void* ws, int64_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * 16-bit convolution family (BASELINE configs[2] bf16 mixed-precision training, configs[4] 16-bit
  * inference; the reference trains / times fp32 and fp16-TensorRT, README.md:176-181).
  *
