@@ -70,6 +70,7 @@ import torch
 
 from . import _lib
 from ._lib import check
+from . import functional as Fn
 from .functional import _stream
 from .postprocessing import RGB_MEAN, RGB_STD, normal_map
 
@@ -267,19 +268,19 @@ class TrainingAugmenter:
         self._no_capture('for this shape')
         slots = []
         for _ in range(self.ring):
-            s = {'params': torch.zeros((n, 8), device=device, dtype=torch.int32)}
+            s = {'params': Fn._zeros((n, 8), device, torch.int32)}
             if 'rgb' in self.modalities:
-                s['rgb'] = torch.empty((n, 3, h, w), device=device, dtype=torch.float32)
+                s['rgb'] = Fn._empty((n, 3, h, w), device, torch.float32)
             if 'depth' in self.modalities:
-                s['depth'] = torch.empty((n, 1, h, w), device=device, dtype=torch.float32)
+                s['depth'] = Fn._empty((n, 1, h, w), device, torch.float32)
             for k, t in labels:
-                s[k] = torch.empty((n, h, w), device=device, dtype=t.dtype)
+                s[k] = Fn._empty((n, h, w), device, t.dtype)
             if orient is not None:
-                s['orientations'] = torch.empty_like(orient)
+                s['orientations'] = Fn._empty(orient.shape, device, orient.dtype)      # (dense: _on_device)
             if scene is not None:
-                s['scene'] = torch.empty_like(scene)
+                s['scene'] = Fn._empty(scene.shape, device, scene.dtype)
             if self.with_normal:
-                s['normal'] = torch.empty((n, h, w, 3), device=device, dtype=torch.float32).permute(0, 3, 1, 2)
+                s['normal'] = Fn._empty((n, h, w, 3), device, torch.float32).permute(0, 3, 1, 2)
             slots.append(s)
         r = self._rings[key] = [0, slots]
         return r

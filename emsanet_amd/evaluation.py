@@ -107,7 +107,7 @@ class ValidationEvaluator:
         key = (name, tuple(shape), dtype, str(device))
         t = self._buf.get(key)
         if t is None:
-            t = self._buf[key] = torch.zeros(tuple(shape), device=device, dtype=dtype)
+            t = self._buf[key] = Fn._zeros(tuple(shape), device, dtype)
         return t
 
     @staticmethod

@@ -288,7 +288,7 @@ class InferenceOutputPacker:
                 raise _lib.EmsaError("InferenceOutputPacker: first call for this device inside a stream "
                                      "capture: run pack() once before capturing")
             lut = None if self.mapping is None else torch.from_numpy(self.mapping).to(device)
-            st = self._dev[key] = (torch.zeros(len(CAUSES), dtype=torch.int64, device=device), lut)
+            st = self._dev[key] = (Fn._zeros((len(CAUSES),), device, torch.int64), lut)
         return st
 
     def _out(self, turn, key, shape, dtype, device):
@@ -298,7 +298,7 @@ class InferenceOutputPacker:
             if torch.cuda.is_current_stream_capturing():
                 raise _lib.EmsaError(f"InferenceOutputPacker: no buffer for '{key}' {tuple(shape)} yet and "
                                      "the stream is capturing: run pack() `ring` times before capturing")
-            t = self._buf[k] = torch.empty(tuple(shape), dtype=dtype, device=device)
+            t = self._buf[k] = Fn._empty(tuple(shape), device, dtype)
         return t
 
     def _lut(self, lut, bound):
@@ -506,9 +506,8 @@ class InferenceOutputPacker:
                                     f"on {dev}, all three of one shape")
             area, cls = area.contiguous(), cls.contiguous()
             slots = area.shape[1]
-            i32 = dict(device=dev, dtype=torch.int32)
-            rank, by_rank, cls_by_rank = (torch.empty((n, slots), **i32) for _ in range(3))
-            count, start = torch.empty(n, **i32), torch.empty(n + 1, **i32)
+            rank, by_rank, cls_by_rank = (Fn._empty((n, slots), dev, torch.int32) for _ in range(3))
+            count, start = Fn._empty((n,), dev, torch.int32), Fn._empty((n + 1,), dev, torch.int32)
             table, size = self._lut(lut, 256)
             check(L.emsa_export_instance_ranks(area.data_ptr(), cls.data_ptr(), Fn._p(table), size, n, slots,
                                                rank.data_ptr(), by_rank.data_ptr(), cls_by_rank.data_ptr(),
@@ -533,7 +532,7 @@ class InferenceOutputPacker:
             start_h = np.concatenate([[0], np.cumsum(count_h)]).astype(np.int32)
             rank, count, start = (torch.from_numpy(a).to(dev) for a in (rank_h, count_h, start_h))
         total = int(start_h[-1])
-        masks = torch.empty((total, H, W), dtype=torch.uint8, device=dev)
+        masks = Fn._empty((total, H, W), dev, torch.uint8)
         check(L.emsa_export_instance_masks(inst.data_ptr(), _LABEL_DTYPES[inst.dtype], n, h, w, H, W,
                                            rank.data_ptr(), slots, count.data_ptr(), start.data_ptr(), total,
                                            Fn._p(masks) if total else None, Fn._stream()),

@@ -57,7 +57,7 @@ class MeanIntersectionOverUnion:
 
     def _buffers(self, device):
         if self._state is None or self._state.device != device:
-            self._state = torch.zeros(self.n_classes ** 2 + 1, device=device, dtype=torch.int64)
+            self._state = Fn._zeros((self.n_classes ** 2 + 1,), device, torch.int64)
         return self._state
 
     def update(self, preds, targets):
@@ -140,13 +140,13 @@ class PanopticQuality:
 
     def _buffers(self, device, n):
         if self._state is None or self._state.device != device:
-            self._state = torch.zeros(4 * self.num_categories + 1, device=device, dtype=torch.int64)
+            self._state = Fn._zeros((4 * self.num_categories + 1,), device, torch.int64)
             self._ws = {}
             self._matches = {}
         ws = self._ws.get(n)
         if ws is None:
             nbytes = _lib.lib().emsa_panoptic_workspace_bytes(n, self.max_segments)
-            ws = self._ws[n] = torch.empty(nbytes, device=device, dtype=torch.uint8)
+            ws = self._ws[n] = Fn._empty((nbytes,), device, torch.uint8)
         return self._state, ws
 
     def update(self, preds, targets):
@@ -185,8 +185,8 @@ class PanopticQuality:
             m = self._matches.get(n)
             if m is None:
                 m = self._matches[n] = (
-                    torch.zeros((n, self.max_segments, 2), device=p.device, dtype=torch.int64),
-                    torch.zeros(n, device=p.device, dtype=torch.int32))
+                    Fn._zeros((n, self.max_segments, 2), p.device, torch.int64),
+                    Fn._zeros((n,), p.device, torch.int32))
             check(L.emsa_panoptic_match_pairs(ws.data_ptr(), n, self.max_segments, k, self.ignored_label,
                                               self.max_instances_per_category, base, base + 8 * k,
                                               base + 16 * k, base + 24 * k, m[0].data_ptr(),
@@ -346,7 +346,7 @@ class MeanAbsoluteAngularError:
 
     def _buffers(self, device):
         if self._state is None or self._state.device != device:
-            self._state = torch.zeros(3, device=device, dtype=torch.int64)
+            self._state = Fn._zeros((3,), device, torch.int64)
         return self._state
 
     def _launch(self, name, vec, count, gt_table, keep, matches, n_matches, max_segments, divisor):
@@ -425,7 +425,7 @@ class MeanAbsoluteNormalError:
 
     def _buffers(self, device):
         if self._state is None or self._state.device != device:
-            self._state = torch.zeros(3, device=device, dtype=torch.int64)
+            self._state = Fn._zeros((3,), device, torch.int64)
         return self._state
 
     def update(self, pred, target):
@@ -484,7 +484,7 @@ def panoptic_targets(semantic, instance, is_thing, label_divisor):
     if s.shape != i.shape or s.device != i.device:
         raise ValueError(f"panoptic_targets: semantic {tuple(s.shape)} vs instance {tuple(i.shape)}")
     table = thing_table(is_thing, s.device)
-    out = torch.empty(s.shape, device=s.device, dtype=torch.int64)
+    out = Fn._empty(s.shape, s.device, torch.int64)
     check(_lib.lib().emsa_panoptic_targets(s.data_ptr(), _LABEL_DTYPES[s.dtype], i.data_ptr(),
                                            _LABEL_DTYPES[i.dtype], table.data_ptr(), len(is_thing),
                                            int(label_divisor), s.numel(), out.data_ptr(), _stream()),

@@ -59,7 +59,7 @@ def softmax_argmax(logits):
         # sample no stride of a (1, C, 1, 1) view says what it is -- batch-1 inference)
         x = torch.cat([logits, logits.new_zeros(n, cp - c)], 1) if cp != c else logits.contiguous()
         score = Fn._empty((n,), x.device)
-        idx = torch.empty((n,), device=x.device, dtype=torch.int64)
+        idx = Fn._empty((n,), x.device, torch.int64)
         check(_lib.lib().emsa_softmax_argmax(Fn._p(x), cp, c, n, Fn._p(score), idx.data_ptr(),
                                              Fn._stream()), 'emsa_softmax_argmax')
         return score, idx
@@ -72,7 +72,7 @@ def softmax_argmax(logits):
         xp[:, :c].copy_(x)
         x = xp[:, :c]
     score = Fn._empty((n, h, w), x.device)
-    idx = torch.empty((n, h, w), device=x.device, dtype=torch.int64)
+    idx = Fn._empty((n, h, w), x.device, torch.int64)
     check(_lib.lib().emsa_softmax_argmax(Fn._p(x), ld, c, n * h * w, Fn._p(score),
                                          idx.data_ptr(), Fn._stream()), 'emsa_softmax_argmax')
     return score, idx
@@ -96,12 +96,12 @@ def instance_centers(heatmap, threshold=0.1, nms_kernel_size=17, top_k=64, foreg
         raise _lib.EmsaError(f"instance_centers: top_k={top_k} outside [1, "
                              f"{L.emsa_center_candidates_max() // 2}]")
     dev = x.device
-    ws_count = torch.empty(2 * n, device=dev, dtype=torch.int32)
+    ws_count = Fn._empty((2 * n,), dev, torch.int32)
     ws_score = Fn._empty((n * cap,), dev)
-    ws_pos = torch.empty(n * cap, device=dev, dtype=torch.int32)
+    ws_pos = Fn._empty((n * cap,), dev, torch.int32)
     centers = Fn._empty((n, top_k, 2), dev)
     scores = Fn._empty((n, top_k), dev)
-    n_centers = torch.empty(n, device=dev, dtype=torch.int32)
+    n_centers = Fn._empty((n,), dev, torch.int32)
     fg = _u8(foreground, 'instance_centers: foreground')
     check(L.emsa_instance_centers(Fn._p(x), Fn.ld_of(x), n, h, w, nms_kernel_size, threshold,
                                   top_k, Fn._p(fg), ws_count.data_ptr(), Fn._p(ws_score),
@@ -123,7 +123,7 @@ def instance_assign(offsets, centers, n_centers, foreground=None, normalized_off
     if centers.dim() != 3 or centers.shape[0] != n or centers.shape[2] != 2 or n_centers.numel() != n:
         raise _lib.EmsaError(f"instance_assign: centers {tuple(centers.shape)} / n_centers "
                              f"{tuple(n_centers.shape)} do not describe {n} images")
-    ids = torch.empty((n, h, w), device=o.device, dtype=torch.int32)
+    ids = Fn._empty((n, h, w), o.device, torch.int32)
     sy, sx = (float(h), float(w)) if normalized_offset else (1.0, 1.0)
     fg = _u8(foreground, 'instance_assign: foreground')
     check(_lib.lib().emsa_instance_assign(Fn._p(o), Fn.ld_of(o), n, h, w, sy, sx, Fn._p(centers),
@@ -219,11 +219,11 @@ def panoptic_merge(semantic_idx, instance_ids, classes_is_thing, top_k=64, label
     thing = thing_table(classes_is_thing, dev)
     sem = _int(semantic_idx, 'panoptic_merge: semantic_idx', torch.int64)
     ids = _int(instance_ids, 'panoptic_merge: instance_ids', torch.int32)
-    ws_votes = torch.empty(n * (top_k + 1) * nc, device=dev, dtype=torch.int32)
-    ws_class = torch.empty(n * (top_k + 1), device=dev, dtype=torch.int32)
-    pan_sem = torch.empty((n, h, w), device=dev, dtype=torch.int64)
-    pan_inst = torch.empty((n, h, w), device=dev, dtype=torch.int32)
-    pan_id = torch.empty((n, h, w), device=dev, dtype=torch.int64)
+    ws_votes = Fn._empty((n * (top_k + 1) * nc,), dev, torch.int32)
+    ws_class = Fn._empty((n * (top_k + 1),), dev, torch.int32)
+    pan_sem = Fn._empty((n, h, w), dev, torch.int64)
+    pan_inst = Fn._empty((n, h, w), dev, torch.int32)
+    pan_id = Fn._empty((n, h, w), dev, torch.int64)
     check(_lib.lib().emsa_panoptic_merge(sem.data_ptr(), ids.data_ptr(), thing.data_ptr(), n, h * w,
                                          nc, top_k, label_divisor, ws_votes.data_ptr(),
                                          ws_class.data_ptr(), pan_sem.data_ptr(),
@@ -239,8 +239,8 @@ def instance_stats(ids, slots, value=None, mask=None):
     n, h, w = ids.shape
     dev = ids.device
     ids = _int(ids, 'instance_stats: ids', torch.int32)
-    area = torch.empty((n, slots), device=dev, dtype=torch.int32)
-    ssum = torch.empty((n, slots), device=dev, dtype=torch.int64) if value is not None else None
+    area = Fn._empty((n, slots), dev, torch.int32)
+    ssum = Fn._empty((n, slots), dev, torch.int64) if value is not None else None
     v = None if value is None else _f32(value, 'instance_stats: value').contiguous()
     mask = _u8(mask, 'instance_stats: mask')
     check(_lib.lib().emsa_instance_stats(ids.data_ptr(), Fn._p(v), Fn._p(mask), n, h * w, slots,
@@ -266,8 +266,8 @@ def panoptic_scores(semantic_score, pan_instance, pan_semantic, center_scores):
     center_scores = _f32(center_scores, 'panoptic_scores: center_scores').contiguous()
     pan_instance = _int(pan_instance, 'panoptic_scores: pan_instance', torch.int32)
     pan_semantic = _int(pan_semantic, 'panoptic_scores: pan_semantic', torch.int64)
-    ws_sum = torch.empty((n, slots), device=dev, dtype=torch.int64)
-    area = torch.empty((n, slots), device=dev, dtype=torch.int32)
+    ws_sum = Fn._empty((n, slots), dev, torch.int64)
+    area = Fn._empty((n, slots), dev, torch.int32)
     inst_sem = Fn._empty((n, slots), dev)
     inst_pan = Fn._empty((n, slots), dev)
     o = [Fn._empty((n, h, w), dev) for _ in range(3)]
@@ -288,8 +288,8 @@ def instance_orientation_sums(orientation, ids, slots, mask=None):
     dev = o.device
     ids = _int(ids, 'instance_orientation_sums: ids', torch.int32)
     mask = _u8(mask, 'instance_orientation_sums: mask')
-    vec = torch.empty((n, slots, 2), device=dev, dtype=torch.int64)
-    cnt = torch.empty((n, slots), device=dev, dtype=torch.int32)
+    vec = Fn._empty((n, slots, 2), dev, torch.int64)
+    cnt = Fn._empty((n, slots), dev, torch.int32)
     check(_lib.lib().emsa_instance_orientation(Fn._p(o), Fn.ld_of(o), ids.data_ptr(), Fn._p(mask),
                                                n, h * w, slots, vec.data_ptr(), cnt.data_ptr(),
                                                Fn._stream()), 'emsa_instance_orientation')

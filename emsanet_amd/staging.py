@@ -28,6 +28,7 @@ from typing import Dict, Iterable, Iterator
 import torch
 
 from . import _lib
+from . import functional as Fn
 from .png import PngFiles
 from .postprocessing import normalize_depth, normalize_rgb
 
@@ -89,7 +90,7 @@ class BatchStager:
                                          "needs pinned memory (DataLoader(pin_memory=True))")
                 buf = slot['bufs'].get(k)
                 if buf is None or buf.shape != v.shape or buf.dtype != v.dtype:
-                    buf = torch.empty(v.shape, dtype=v.dtype, device=self.device)
+                    buf = Fn._empty(v.shape, self.device, v.dtype)
                     slot['bufs'][k] = buf
                 buf.copy_(v, non_blocking=True)
                 self.bytes_staged += v.numel() * v.element_size()
@@ -114,8 +115,8 @@ class BatchStager:
         n = files.data.numel()
         if buf is None or buf[0].numel() < n or buf[1].numel() != files.m + 1:
             size = 1 << max(12, (n - 1).bit_length())
-            buf = slot['bufs'][name] = (torch.empty(size, dtype=torch.uint8, device=self.device),
-                                        torch.empty(files.m + 1, dtype=torch.int64, device=self.device))
+            buf = slot['bufs'][name] = (Fn._empty((size,), self.device, torch.uint8),
+                                        Fn._empty((files.m + 1,), self.device, torch.int64))
         buf[0][:n].copy_(files.data, non_blocking=True)
         buf[1].copy_(files.offsets, non_blocking=True)
         self.bytes_staged += n

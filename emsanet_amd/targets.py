@@ -48,6 +48,7 @@ import torch
 
 from . import _lib
 from ._lib import EmsaNormalScale, EmsaTargetScale, check
+from . import functional as Fn
 from .functional import _stream
 from .postprocessing import normal_map, thing_table
 
@@ -163,7 +164,7 @@ class TrainingTargetGenerator:
             gauss = torch.from_numpy(np.concatenate(tabs)).to(device) if tabs else None
             c = self._tables[device] = (thing_table(self.is_thing, device),
                                         thing_table(self.use_orientation, device), gauss,
-                                        torch.zeros(2, device=device, dtype=torch.int32))
+                                        Fn._zeros((2,), device, torch.int32))
         return c
 
     def _slots(self, device, n, h, w):
@@ -183,34 +184,32 @@ class TrainingTargetGenerator:
                 hs, ws = h // s, w // s
                 e.scale, e.sigma = s, sg
                 if sem:
-                    t = torch.empty((n, hs, ws), device=device, dtype=torch.int64)
+                    t = Fn._empty((n, hs, ws), device, torch.int64)
                     e.semantic = t.data_ptr()
                     sem_out.append(t)
                 if inst:
-                    d = {'center': torch.empty((n, 1, hs, ws), device=device, dtype=torch.float32),
+                    d = {'center': Fn._empty((n, 1, hs, ws), device, torch.float32),
                          # (N,2,H_s,W_s) with channels-last strides: the loss's permute is a view
-                         'offset': torch.empty((n, hs, ws, 2), device=device,
-                                               dtype=torch.float32).permute(0, 3, 1, 2),
-                         'foreground': torch.empty((n, hs, ws), device=device, dtype=torch.bool)}
+                         'offset': Fn._empty((n, hs, ws, 2), device, torch.float32).permute(0, 3, 1, 2),
+                         'foreground': Fn._empty((n, hs, ws), device, torch.bool)}
                     e.center, e.offset = d['center'].data_ptr(), d['offset'].data_ptr()
                     e.foreground = d['foreground'].data_ptr()
                     if self.with_orientation:
-                        d['orientation'] = torch.empty((n, hs, ws), device=device, dtype=torch.float32)
-                        d['orientation_foreground'] = torch.empty((n, hs, ws), device=device,
-                                                                  dtype=torch.bool)
+                        d['orientation'] = Fn._empty((n, hs, ws), device, torch.float32)
+                        d['orientation_foreground'] = Fn._empty((n, hs, ws), device, torch.bool)
                         e.orientation = d['orientation'].data_ptr()
                         e.orientation_foreground = d['orientation_foreground'].data_ptr()
                     inst_out.append(d)
             nbytes = L.emsa_targets_workspace_bytes(n, len(self.plan), self.max_instances) if self.plan else 0
             slots.append({'desc': desc, 'semantic': sem_out, 'instance': inst_out,
-                          'ws': torch.zeros(nbytes, device=device, dtype=torch.uint8),
-                          'scene': torch.empty(n, device=device, dtype=torch.int64)})
+                          'ws': Fn._zeros((nbytes,), device, torch.uint8),
+                          'scene': Fn._empty((n,), device, torch.int64)})
             if self.with_normal:
                 ndesc = (EmsaNormalScale * len(self.normal_scales))()
                 normal_out = []
                 for e, s in zip(ndesc, self.normal_scales):
                     # (N,3,H_s,W_s) with channels-last strides, like 'offset'
-                    t = torch.empty((n, h // s, w // s, 3), device=device, dtype=torch.float32)
+                    t = Fn._empty((n, h // s, w // s, 3), device, torch.float32)
                     e.scale, e.out = s, t.data_ptr()
                     normal_out.append(t.permute(0, 3, 1, 2))
                 slots[-1].update(normal_desc=ndesc, normal=normal_out)

@@ -56,6 +56,37 @@ def merge_candidates(heat, threshold, kernel, top_k, foreground=None):
     return flat.sum(-1).clamp(max=top_k).sum(-1)
 
 
+CAP_TOP_K = 8
+
+
+def cap_heat(seed=23):
+    """33 x 64 = 2112 pixels: two whole chunks and one of 64 pixels, so with top_k = 8 the candidate lists
+    hold cap = 3 * 8 = 24 entries per image.  Window 1, threshold 0.1: a pixel survives iff it is set.
+    Distinct scores in [0.2, 1), everything else 0.  Survivors per chunk:
+      image 0: 8, 8, 8   the candidate count equals cap, nothing is cut
+      image 1: 9, 8, 8   cap + 1: the ninth of the first chunk (its lowest score) is cut
+      image 2: 5, 3, 0   top_k survivors exactly: every centre slot is used, none padded
+    the last pixel of the map (the last of the partial chunk) is set in images 0 and 1"""
+    g = torch.Generator().manual_seed(seed)
+    h, w = 33, 64
+    counts = ((8, 8, 8), (9, 8, 8), (5, 3, 0))
+    heat = torch.zeros(len(counts), 1, h, w)
+    total = sum(sum(c) for c in counts)
+    scores = (0.2 + 0.8 * (torch.randperm(total, generator=g).double() + 0.5) / total).float()
+    k = 0
+    for i, per_chunk in enumerate(counts):
+        flat = heat[i, 0].view(-1)
+        for c, m in enumerate(per_chunk):
+            size = min(CHUNK, h * w - c * CHUNK)
+            pos = torch.randperm(size, generator=g)[:m] + c * CHUNK
+            if m and c == 2:
+                pos[0] = h * w - 1
+            flat[pos.unique()[:m]] = scores[k:k + m]
+            assert int((flat[c * CHUNK:c * CHUNK + size] > 0).sum()) == m
+            k += m
+    return heat
+
+
 def blob_heat(n, h, w, seed, n_blobs=12):
     g = torch.Generator().manual_seed(seed)
     yy, xx = torch.meshgrid(torch.arange(h).float(), torch.arange(w).float(), indexing='ij')

@@ -155,3 +155,26 @@ def rectangles_scene(n, h, w, count, seed, cell=20, max_instances=256, big_first
             rect(sem[i], cy - hy, cy + hy + ey, cx - hx, cx + hx + ex, (1, 2, 4, 5)[k % 4])
             rect(inst[i], cy - hy, cy + hy + ey, cx - hx, cx + hx + ex, k + 1)
     return sem, inst
+
+
+def corner_scene(max_instances=256):
+    """(semantic, instance, orientations, scene) at 32x32, N = 2: the side scales are 1x1, 2x2 and 4x4
+    maps (1, 4 and 16 pixels: none a multiple of 64), and the full-scale window (radius 25) of every
+    instance is clipped on two sides.  Image 0: a 3x3 thing at each of the four image corners, the
+    bottom-right one with the last id of the table, max_instances - 1; only the top-left one is
+    sampled by the side scales.  Image 1: one instance, again the last id, over the whole image: its
+    centre is (0, 0) at 1x1 and at 2x2 (mean 0.5, half to even) and (2, 2) at 4x4 (mean 1.5)."""
+    n, h, w = 2, 32, 32
+    sem = np.full((n, h, w), 3, np.int64)
+    inst = np.zeros((n, h, w), np.int64)
+    ori = np.full((n, max_instances), np.nan, np.float32)
+    top = max_instances - 1
+    for y0, x0, cls, k, angle in ((0, 0, 1, 1, 0.25), (0, 29, 2, 2, None), (29, 0, 4, top - 1, -1.5),
+                                  (29, 29, 1, top, 2.5)):
+        rect(sem[0], y0, y0 + 2, x0, x0 + 2, cls)
+        rect(inst[0], y0, y0 + 2, x0, x0 + 2, k)
+        if angle is not None:
+            ori[0, k] = angle
+    sem[1], inst[1] = 4, top
+    ori[1, top] = -0.75
+    return sem, inst, ori, np.array([2, 7], np.int64)

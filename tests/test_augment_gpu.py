@@ -12,7 +12,13 @@ is about 10x the round-off bound and 170x below a wrong pixel (the float32 NumPy
 
 Shapes: 37x53 -> 32x48 (one tile, the clamped border rows and columns of an up-scale), 60x80 -> 32x48
 (down-scaling), 96x128 = crop, 480x640 bs 2 (many tiles in x and y, whole and partial), and a crop width
-of 50 (no multiple of 4: the scalar-store path and a 2-pixel vector tail)."""
+of 50 (no multiple of 4: the scalar-store path and a 2-pixel vector tail).
+
+Every test runs on the guarded arena of tests/guard.py, once per payload byte -- as
+`test_x` on 0xFF and as its twin `test_x_poison00` on 0x00 -- (label maps of every
+integer dtype and the drawn table are compared exactly): the ring slots lie between two bands of 0xFF,
+and the raw frames, label maps and forced parameter rows are placed with `guard.put`, so that a gather
+past the last source row or column reads poison."""
 import os
 import sys
 
@@ -22,6 +28,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import augment_reference as R   # noqa: E402
+import guard   # noqa: E402
+from guard import guard_allocations  # noqa: E402,F401  (autouse: poisoned, guard-banded allocations)
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -47,7 +55,7 @@ def _aug(h, w, smin=1.0, smax=1.4, tasks=ALL_TASKS, modalities=('rgb', 'depth'),
 
 
 def _dev(batch, keys=None):
-    return {k: torch.from_numpy(np.ascontiguousarray(v)).to(DEV) for k, v in batch.items()
+    return {k: guard.put(torch.from_numpy(np.ascontiguousarray(v)).to(DEV)) for k, v in batch.items()
             if keys is None or k in keys}
 
 
@@ -120,6 +128,7 @@ def test_drawn_parameters(batches, case, hsv):
     amps = AMPS if hsv else (0.0, 0.0, 0.0)
     aug = _aug(h, w, smin, smax, seed=11, hsv_jitter=amps)
     got = aug.apply(_dev(batches[case]))
+    guard.check()
     table = aug.last_params().numpy()
     want = R.draw_table(11, 0, n, hs, ws, h, w, aug.q_min, aug.q_max, 0.5, amps)
     assert np.array_equal(table, want)
@@ -158,6 +167,7 @@ def test_every_label_dtype(batches, dt_sem, dt_inst, w):
     b['instance'] = b['instance'].astype(NP_DTYPES[dt_inst])
     aug = _aug(32, w, seed=3)
     got = aug.apply(_dev(b))
+    guard.check()
     assert got['semantic'].dtype == dt_sem and got['instance'].dtype == dt_inst
     assert_augmented(got, b, aug.last_params().numpy(), 32, w, True)
 
@@ -199,10 +209,11 @@ def test_forced_parameter_rows():
     table = R.pack_rows(rows)
     b = _stripes(len(rows), hs, ws)
     dev = _dev(b)
-    params = torch.from_numpy(table).to(DEV)
+    params = guard.put(torch.from_numpy(table).to(DEV))
     for hsv in (True, False):
         aug = _aug(h, w, hsv_jitter=AMPS if hsv else (0.0, 0.0, 0.0))
         got = aug.apply(dev, params=params)
+        guard.check()
         assert np.array_equal(aug.last_params().numpy(), table)
         ref = assert_augmented(got, b, table, h, w, hsv)
         assert aug.state_dict()['step'] == 0                      # a forced table draws nothing
@@ -216,6 +227,28 @@ def test_forced_parameter_rows():
     for k in first:
         assert first[k].data_ptr() != second[k].data_ptr(), k
         assert _same(first[k], second[k]), k
+
+
+@pytest.mark.parametrize('w', [48, 50])
+def test_forced_far_corner_with_flip(w):
+    """the crop in the far corner of the resized frame, flipped, at scale 1 and at the maximum scale: the
+    last source row and column are the last ones gathered (the bilinear taps beyond are clamped), at a
+    crop width that is a multiple of the 4-pixel vector and at one that is not (50)"""
+    hs, ws, h = 37, 53, 32
+    hm, wm = (hs * 1434 + 512) >> 10, (ws * 1434 + 512) >> 10
+    a = [np.float32(v) for v in AMPS]
+    rows = [(hs, ws, hs - h, ws - w, 1, a[0], -a[1], a[2]),
+            (hm, wm, hm - h, wm - w, 1, -a[0], a[1], -a[2]),
+            (hm, wm, hm - h, wm - w, 0, 0.0, 0.0, 0.0)]
+    table = R.pack_rows(rows)
+    b = _stripes(len(rows), hs, ws)
+    params = guard.put(torch.from_numpy(table).to(DEV))
+    for hsv in (True, False):
+        aug = _aug(h, w, hsv_jitter=AMPS if hsv else (0.0, 0.0, 0.0))
+        got = aug.apply(_dev(b), params=params)
+        guard.check()
+        assert np.array_equal(aug.last_params().numpy(), table)
+        assert_augmented(got, b, table, h, w, hsv)
 
 
 def test_ring_keeps_the_previous_outputs(batches):
@@ -294,6 +327,7 @@ def test_apply_and_generate_capture_into_a_graph():
         tables.append(table)
     assert not np.array_equal(tables[0], tables[1])
     gen.check()
+    guard.check()                            # (every captured buffer was made by the warm-up step)
 
 
 def test_batch_stager_augments_and_generates():
@@ -313,6 +347,7 @@ def test_batch_stager_augments_and_generates():
     staged = list(BatchStager(host_batches(), DEV, augmenter=_aug(h, w, seed=5, ring=3),
                               target_generator=_generator(args, ring=3)))
     torch.cuda.synchronize()
+    guard.check()                            # the stager's device buffers, the augmenter's and the generator's rings
     aug, gen = _aug(h, w, seed=5), _generator(args)
     assert len(staged) == 3
     for j, (s, b) in enumerate(zip(staged, raw)):
@@ -372,3 +407,7 @@ def test_training_step_on_an_augmented_batch():
     gen.check()
     assert all(np.isfinite(v) for v in l_aug.values()) and np.isfinite(t_aug) and t_aug > 0
     assert l_aug['semantic'] != l_plain['semantic']
+
+
+# every test above once more as `<name>_poison00`, on 0x00 payloads (True, 255 and -1 are legal values)
+guard.second_payload(globals())

@@ -4,7 +4,14 @@ NumPy restatement of tests/evaluation_reference.py.
 Bounds: every count is an integer and must match exactly.  The angular-error sum is int64 fixed point
 (2^-40 rad) with each term rounded once: |dev - ref| <= count units (half a unit per term for the
 rounding, doubled as margin; the device's double atan2 differs from NumPy's by ~1e-16, far below a
-unit).  Results within 1e-9 (one unit is 5.2e-11 deg), the bar tests/test_metrics_gpu.py uses."""
+unit).  Results within 1e-9 (one unit is 5.2e-11 deg), the bar tests/test_metrics_gpu.py uses.
+
+Every test runs on the guarded arena of tests/guard.py, once per payload byte -- as
+`test_x` on 0xFF and as its twin `test_x_poison00` on 0x00 -- (counts, match pairs and
+confusion matrices are compared exactly): the evaluator's buffers, the metric states and workspaces lie
+between two bands of 0xFF, hand-made inputs are placed with `guard.put`.  The model whose prediction the
+evaluator tests read is built by a module fixture, before the arena is installed; the two tests that
+run a model themselves are opted out (guard.OPT_OUT)."""
 import math
 import os
 import sys
@@ -15,14 +22,16 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import evaluation_reference as E   # noqa: E402
+import guard   # noqa: E402
 import test_metrics as R   # noqa: E402
+from guard import guard_allocations  # noqa: E402,F401  (autouse: poisoned, guard-banded allocations)
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
 
 
 def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    return guard.put(torch.from_numpy(np.ascontiguousarray(a)).to(DEV))    # flush between two bands of 0xFF
 
 
 def _stream():
@@ -39,11 +48,12 @@ def test_match_pairs_equal_match_and_export_the_reference_pairs(name, images):
     ref.update(pred, target)
     L, T, K = _lib.lib(), 256, R.SCENE_CATEGORIES
     p, t = _dev(pred), _dev(target)
-    ws = torch.empty(L.emsa_panoptic_workspace_bytes(images, T), device=DEV, dtype=torch.uint8)
-    a = torch.zeros(4 * K + 1, device=DEV, dtype=torch.int64)
-    b = torch.zeros(4 * K + 1, device=DEV, dtype=torch.int64)
-    matches = torch.full((images, T, 2), -7, device=DEV, dtype=torch.int64)
-    n_matches = torch.full((images,), -7, device=DEV, dtype=torch.int32)
+    from emsanet_amd import functional as Fn
+    ws = Fn._empty((L.emsa_panoptic_workspace_bytes(images, T),), DEV, torch.uint8)      # (the arena's)
+    a = guard.put(torch.zeros(4 * K + 1, device=DEV, dtype=torch.int64))
+    b = guard.put(torch.zeros(4 * K + 1, device=DEV, dtype=torch.int64))
+    matches = guard.put(torch.full((images, T, 2), -7, device=DEV, dtype=torch.int64))
+    n_matches = guard.put(torch.full((images,), -7, device=DEV, dtype=torch.int32))
     assert L.emsa_panoptic_pairs(p.data_ptr(), t.data_ptr(), images, h * w, T, ws.data_ptr(),
                                  a.data_ptr() + 32 * K, _stream()) == 0
     assert L.emsa_panoptic_match(ws.data_ptr(), images, T, K, 0, div, *(a.data_ptr() + 8 * K * j for j in range(4)),
@@ -52,6 +62,7 @@ def test_match_pairs_equal_match_and_export_the_reference_pairs(name, images):
                                        *(b.data_ptr() + 8 * K * j for j in range(4)), matches.data_ptr(),
                                        n_matches.data_ptr(), b.data_ptr() + 32 * K, _stream()) == 0
     torch.cuda.synchronize()
+    guard.check()
     assert int(a[:K].sum()) == sum(ref.tp) >= images
     assert torch.equal(a, b)                                            # tp / fn / fp / iou_sum, flags
     assert a[:K].tolist() == ref.tp and a[K:2 * K].tolist() == ref.fn and a[2 * K:3 * K].tolist() == ref.fp
@@ -84,12 +95,14 @@ def test_update_with_matches_is_update_and_survives_overflow():
     crowded = (4000 + grid).astype(np.int64)[None]
     m = pq(max_segments=8)
     matches, n_matches = m.update_with_matches(_dev(crowded), _dev(crowded))
+    guard.check()                                                       # the pairs too many were stored nowhere
     assert matches.shape == (1, 8, 2) and 0 <= int(n_matches[0]) <= 8
     with pytest.raises(ValueError, match='overflow'):
         m.compute()
     few = (4000 + (grid - 1) % 8).astype(np.int64)[None]               # a table exactly full
     m.reset()
     matches, n_matches = m.update_with_matches(_dev(few), _dev(few))
+    guard.check()
     assert int(n_matches[0]) == 8 and m.counts()['tp'][4] == 8
     got = sorted(tuple(r) for r in matches[0].tolist())
     assert got == [(4000 + j, 4000 + j) for j in range(8)]
@@ -179,6 +192,7 @@ def test_angular_error_both_modes(n, h, w, layout):
     keep8 = keep[:, :slots].astype(np.uint8)
     m, ref = MeanAbsoluteAngularError(), E.AngularErrorReference()
     m.update_matched(vec, cnt, _dev(gt), _dev(matches), _dev(nm), 1000, keep=_dev(keep8))
+    guard.check()
     ref.update_matched(rvec, rcnt, gt, pairs, 1000, keep8)
     assert not ref.flag
     _check_angle(m, ref, f'matched {n}x{h}x{w} {layout}')
@@ -197,6 +211,7 @@ def test_angular_error_flags_an_id_equal_to_max_instances():
     rvec, rcnt = E.orientation_sums_reference(ori, ids, MAX_INST + 1, fg)
     m, ref = MeanAbsoluteAngularError(), E.AngularErrorReference()
     m.update(vec, cnt, _dev(gt))
+    guard.check()                                                        # id == MAX_INST: flagged, stored nowhere
     ref.update(rvec, rcnt, gt)
     assert ref.flag
     with pytest.raises(ValueError, match='outside the orientation tables'):
@@ -303,6 +318,13 @@ def _setup():
     return _CACHE['full']
 
 
+@pytest.fixture(scope='module')
+def full_setup():
+    """`_setup()` ahead of the function-scoped guard fixture: the model and its eval forward passes (the
+    whole model) run on the plain allocator, the evaluator under test on the arena"""
+    return _setup()
+
+
 def _host_inputs(prediction, batch, fullres=False):
     """the evaluator's inputs as host arrays for E.EvaluatorReference"""
     s = '_fullres' if fullres else ''
@@ -355,12 +377,14 @@ def _nothing_vacuous(ref):
     assert ref.cm_scene[1:, 1:].sum() >= 1 and ref.cm_scene[0].sum() >= 1
 
 
+@pytest.mark.usefixtures('full_setup')
 def test_evaluator_against_the_numpy_composition():
     from emsanet_amd import ValidationEvaluator
     args, cfg, model, batch, prediction = _setup()
     div = model.decoders['panoptic_helper'].postprocessing.max_instances_per_category
     ev = ValidationEvaluator(args, cfg, label_divisor=div)
     ev.update(prediction, batch)
+    guard.check()
     ref = _reference(args, cfg, div)
     ref.update(*_host_inputs(prediction, batch))
     _nothing_vacuous(ref)
@@ -373,6 +397,7 @@ def test_evaluator_against_the_numpy_composition():
     assert all(int(s.abs().sum()) == 0 for s in ev.state().values())
 
 
+@pytest.mark.usefixtures('full_setup')
 def test_evaluator_is_consistent_with_the_existing_outputs():
     """the two angular errors from the per-sample dictionaries the post-processing already yields;
     semantic_miou and panoptic_all_deeplab_pq from the existing classes on the same maps"""
@@ -418,6 +443,7 @@ def _slice(d, sel):
     return {k: v[sel] for k, v in d.items() if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == BS}
 
 
+@pytest.mark.usefixtures('full_setup')
 def test_evaluator_batch_equals_single_images_and_repeats():
     from emsanet_amd import ValidationEvaluator
     args, cfg, model, batch, prediction = _setup()
@@ -433,6 +459,7 @@ def test_evaluator_batch_equals_single_images_and_repeats():
         assert torch.equal(sa[k], sb[k]) and torch.equal(sa[k], sc[k]), k
 
 
+@pytest.mark.usefixtures('full_setup')
 def test_evaluator_update_captures_into_a_graph():
     """warm-up, capture one update() on static inputs, replay it on two further batches (the samples in
     another order) copied into them: the state is the eager one, compute() the reference's"""
@@ -467,8 +494,10 @@ def test_evaluator_update_captures_into_a_graph():
     for k in se:
         assert int(se[k].abs().sum()) > 0 and torch.equal(se[k], sg[k]), k
     _check_evaluator(ev, ref, 'graph')
+    guard.check()                                    # (every buffer of `ev` was made by the warm-up update)
 
 
+@pytest.mark.usefixtures('full_setup')
 def test_evaluator_reads_fullres_entries_for_larger_label_maps():
     from emsanet_amd import ValidationEvaluator
     args, cfg, model, batch, prediction = _setup()
@@ -489,6 +518,7 @@ def test_evaluator_reads_fullres_entries_for_larger_label_maps():
         ValidationEvaluator(args, cfg).update(p, small)
 
 
+@pytest.mark.usefixtures('full_setup')
 def test_evaluator_keys_follow_the_tasks():
     from util import deterministic_state_dict
     from emsanet_amd import ValidationEvaluator, full_args
@@ -513,3 +543,7 @@ def test_evaluator_keys_follow_the_tasks():
     for k in want:
         assert abs(got[k] - want[k]) <= 1e-9, k
     assert sorted(ev.state()) == ['scene', 'semantic_miou']
+
+
+# every test above once more as `<name>_poison00`, on 0x00 payloads (True, 255 and -1 are legal values)
+guard.second_payload(globals())

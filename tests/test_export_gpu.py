@@ -1,7 +1,14 @@
 """Device-side packing of the inference outputs (emsanet_amd/export.py, csrc/export.hip) against the NumPy
 restatement of tests/export_reference.py.  Every output is integer or ONE fp32 add of exactly
 representable operands' images, so every comparison is exact equality (np.array_equal), the fp32
-outputs included; the counters must agree as well."""
+outputs included; the counters must agree as well.
+
+Every test runs on the guarded arena of tests/guard.py, once per payload byte -- as
+`test_x` on 0xFF and as its twin `test_x_poison00` on 0x00 -- (uint8 maps hold 255 and
+the rank tables -1: what 0xFF reads as): the packer's ring buffers, the rank / count / start tables and
+the mask stack -- sized by a count read back from the device -- lie between two bands of 0xFF, and the
+source maps, tables and the destinations a test hands in are placed with `guard.put`.  The model whose
+prediction three tests pack is built by a module fixture, before the arena is installed."""
 import os
 import sys
 
@@ -11,6 +18,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import export_reference as X   # noqa: E402
+import guard   # noqa: E402
+from guard import guard_allocations  # noqa: E402,F401  (autouse: poisoned, guard-banded allocations)
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -18,7 +27,7 @@ NP_LABEL = {'int64': np.int64, 'int32': np.int32, 'uint8': np.uint8}
 
 
 def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    return guard.put(torch.from_numpy(np.ascontiguousarray(a)).to(DEV))    # flush between two bands of 0xFF
 
 
 def _np(t):
@@ -61,10 +70,11 @@ def _run_all_kinds(n, h, w, H, W, label, seed, max_depth=2500.5):
     table = _table()
     lut = _dev(table)
     d16, d32 = _dev(depth), _dev(depth.astype(np.float32))
-    counters = torch.zeros(4, dtype=torch.int64, device=DEV)
+    counters = guard.put(torch.zeros(4, dtype=torch.int64, device=DEV))
     def new(dt, *tail):                                                  # pre-filled: every byte must be written
         shape = (n, H, W) + tail
-        return torch.full(shape[:-1] + (shape[-1] * dt.itemsize,), 77, dtype=torch.uint8, device=DEV).view(dt)
+        return guard.put(torch.full(shape[:-1] + (shape[-1] * dt.itemsize,), 77, dtype=torch.uint8,
+                                    device=DEV)).view(dt)
     s, i, p, sc = _dev(sem), _dev(inst), _dev(pan), _dev(score)
     jobs = [E.PackJob(E.LABEL_U8, s, new(torch.uint8), lut=lut, lut_size=41, add=1),
             E.PackJob(E.LABEL_U8, s, new(torch.uint8), lut_size=41, depth=d16, max_depth=max_depth),
@@ -88,6 +98,7 @@ def _run_all_kinds(n, h, w, H, W, label, seed, max_depth=2500.5):
             X.class_score_f32(sem, score, hw, c, table, add=1),
             X.class_score_f32(inst, score, hw, c, lut_size=0)]
     torch.cuda.synchronize()
+    guard.check()
     for k, (j, ref) in enumerate(zip(jobs, want)):
         got = _np(j.dst)
         assert got.dtype == ref.dtype and got.shape == ref.shape, (k, got.dtype, got.shape, ref.shape)
@@ -120,9 +131,10 @@ def test_an_unaligned_source_view_takes_the_gather_path():
     rng = np.random.RandomState(3)
     flat = rng.randint(0, 40, 2 * 8 * 16 + 1).astype(np.uint8)
     src = _dev(flat)[1:].view(2, 8, 16)                                  # 1 byte off the allocation
-    dst = torch.empty((2, 8, 16), dtype=torch.uint8, device=DEV)
-    counters = torch.zeros(4, dtype=torch.int64, device=DEV)
+    dst = guard.put(torch.full((2, 8, 16), 77, dtype=torch.uint8, device=DEV))
+    counters = guard.put(torch.zeros(4, dtype=torch.int64, device=DEV))
     E.export_pack([E.PackJob(E.LABEL_U8, src, dst, lut_size=256, add=1)], counters)
+    guard.check()
     assert np.array_equal(_np(dst), flat[1:].reshape(2, 8, 16) + 1) and not counters.any()
 
 
@@ -198,12 +210,61 @@ def test_instance_outputs_small(h, w, H, W, label):
         assert np.array_equal(_np(masks), want)
         assert got_lines == lines and len(lines[0]) == 3 and lines[1] == []
         assert out.start == [0, 3, 3] and masks[out.start[1]:out.start[2]].shape[0] == 0
+        guard.check()
     assert want[1].sum() == 0 and want[0].sum() > 0 and want[2].sum() > 0
     packer.check()
     # nobody owns a pixel: an empty stack
     meta.device_tables = {'area': _dev(area * 0), 'instance_class': _dev(cls), 'panoptic_score': _dev(score)}
     out = packer.instance_outputs(pred, None, ['a', 'b'])
     assert tuple(out.masks.shape) == (0, h, w) and out.lines == [[], []]
+    guard.check()
+
+
+@pytest.mark.parametrize('label', ['int32', 'uint8'])
+@pytest.mark.parametrize('used', ['every_slot', 'one', 'none'])
+def test_instance_ranks_table_ends_and_stack_totals(used, label):
+    """9 slots, N = 3, 7 x 13 -> 7 x 13.  every_slot: all eight ids of every sample are ranked, the last
+    rank of the last sample is the last entry of every table and the last plane of a 24-plane stack.
+    one: a single instance in the last sample, id 8: a stack of exactly one plane behind two empty
+    slices.  none: no slot used at all: a stack of 0 planes, and the mask kernel gets no pointer"""
+    from emsanet_amd import InferenceOutputPacker
+    n, h, w, slots = 3, 7, 13, 9
+    rng = np.random.RandomState(len(used))
+    inst = np.zeros((n, h, w), NP_LABEL[label])
+    area = np.zeros((n, slots), np.int32)
+    if used == 'every_slot':
+        inst[:] = rng.randint(0, slots, (n, h, w))
+        inst[:, 0, :slots] = np.arange(slots)                            # every id has a pixel
+        inst[-1, -1, -1] = slots - 1
+    elif used == 'one':
+        inst[-1, -2:, -3:] = slots - 1
+    for i in range(n):
+        for j in range(1, slots):
+            area[i, j] = (inst[i] == j).sum()
+    cls = np.where(area > 0, rng.randint(0, 40, (n, slots)), -1).astype(np.int32)
+    score = rng.rand(n, slots).astype(np.float32)
+    table = _table()
+    meta = _Meta([{j: {'area': int(area[i, j]), 'semantic_idx': int(cls[i, j]) + 1,
+                       'panoptic_score': float(score[i, j])} for j in range(1, slots) if area[i, j]}
+                  for i in range(n)])
+    meta.device_tables = {'area': _dev(area), 'instance_class': _dev(cls), 'panoptic_score': _dev(score)}
+    names = ['s_000', 's_001', 's_002']
+    rank, count, start = X.instance_ranks(area)
+    total = {'every_slot': n * (slots - 1), 'one': 1, 'none': 0}[used]
+    assert int(start[-1]) == total and (used != 'every_slot' or (rank[:, 1:] >= 0).all())
+    want = X.instance_masks(inst, rank, count, start, (h, w))
+    lines = [X.instance_lines(meta[i], b, table) for i, b in enumerate(names)]
+    pred = {'panoptic_segmentation_deeplab_instance_idx': _dev(inst),
+            'panoptic_segmentation_deeplab_instance_meta': meta}
+    packer = InferenceOutputPacker(formats='scannet-instance', semantic_class_mapping=table)
+    out = packer.instance_outputs(pred, None, names)
+    guard.check()
+    assert out.masks.dtype == torch.uint8 and tuple(out.masks.shape) == (total, h, w)
+    assert np.array_equal(_np(out.masks), want)
+    assert out.lines == lines and out.start == start.tolist()
+    if total:
+        assert want[-1].any() and want[-1, -1, -1] == 255                # the last plane's last byte is set
+    packer.check()
 
 
 # ---- counters -------------------------------------------------------------------------------------
@@ -292,6 +353,13 @@ def _setup():
     return _CACHE['full']
 
 
+@pytest.fixture(scope='module')
+def full_setup():
+    """`_setup()` ahead of the function-scoped guard fixture: the model and its eval forward pass (the
+    whole model) run on the plain allocator, the packer under test on the arena"""
+    return _setup()
+
+
 def _host(d):
     out = {}
     for k, v in d.items():
@@ -302,6 +370,7 @@ def _host(d):
     return out
 
 
+@pytest.mark.usefixtures('full_setup')
 @pytest.mark.parametrize('shift,mapped', [(1000, True), (1 << 16, False)])
 def test_packer_end_to_end_on_the_model_prediction(shift, mapped):
     from emsanet_amd import InferenceOutputPacker
@@ -314,6 +383,7 @@ def test_packer_end_to_end_on_the_model_prediction(shift, mapped):
     host = packer.to_host(packed)
     packer.check()
     got = host.synchronize()
+    guard.check()
     want, c = X.pack_reference(_host(prediction), _host(batch), E.FORMATS, div, table, **kw)
     assert not c.any()
     assert set(want) == set(got) - {'mapping/pred_panoptic_instance_meta'} and len(want) == 10
@@ -345,9 +415,11 @@ def test_packer_end_to_end_on_the_model_prediction(shift, mapped):
     for p in (prediction, {**prediction, 'panoptic_segmentation_deeplab_instance_meta': meta}):
         out = packer.instance_outputs(p, batch, names)
         assert np.array_equal(_np(out.masks), masks) and out.lines == lines and out.start == start.tolist()
+        guard.check()
     packer.check()
 
 
+@pytest.mark.usefixtures('full_setup')
 def test_pack_replayed_from_a_graph_behind_the_eval_forward():
     """`GraphedInference(..., do_postprocessing=True, after=packer.pack)`: the replay's packed outputs are
     the eager ones on two inputs, in the same buffers every time; eager calls allocate nothing after the
@@ -389,6 +461,7 @@ def test_pack_replayed_from_a_graph_behind_the_eval_forward():
     packer.check()
 
 
+@pytest.mark.usefixtures('full_setup')
 def test_to_host_copies_into_the_ring_set_the_outputs_came_from():
     from emsanet_amd import InferenceOutputPacker
     model, batch, prediction, div = _setup()
@@ -425,3 +498,7 @@ def test_instance_outputs_refuses_malformed_device_tables():
         with pytest.raises(TypeError, match=r"device_tables\['"):
             packer.instance_outputs({'panoptic_segmentation_deeplab_instance_idx': inst,
                                      'panoptic_segmentation_deeplab_instance_meta': meta}, None, ['a', 'b'])
+
+
+# every test above once more as `<name>_poison00`, on 0x00 payloads (True, 255 and -1 are legal values)
+guard.second_payload(globals())

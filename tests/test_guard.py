@@ -206,3 +206,140 @@ def test_call_site_names_the_wrapper_in_the_package(monkeypatch):
     Fn.add(x, x)
     assert re.match(r'functional\.py:add:\d+$', a._live[0][3]), a._live[0][3]
     a.check()
+
+
+# -- the second payload byte: 0xFF is a legal value of the integer outputs ------------------------------
+INT_POISON = [(torch.int64, -1, 0), (torch.int32, -1, 0), (torch.uint8, 255, 0), (torch.bool, True, False)]
+
+
+@pytest.mark.parametrize('dtype, under_ff, under_00', INT_POISON)
+def test_integer_poison_values_under_both_payloads(dtype, under_ff, under_00):
+    assert GuardedArena(G).payload == 0xFF               # the default: existing behaviour
+    for payload, want in ((0xFF, under_ff), (0x00, under_00)):
+        a = GuardedArena(G, payload=payload)
+        t = a.alloc((3, 7), 'cpu', dtype)
+        assert t.dtype == dtype and bool((t == want).all()), (dtype, payload, t)
+        buf, off, nbytes = _buffer_of(a)
+        assert bool((buf[off:off + nbytes] == payload).all())
+        # the bands stay 0xFF whatever the payload byte is
+        assert bool((buf[:off] == 0xFF).all()) and bool((buf[off + nbytes:] == 0xFF).all())
+        assert a.check() == 1
+
+
+def test_between_the_payloads_every_unwritten_element_differs():
+    """whatever an integer output is expected to hold, it is not both 0xFF.. and 0x00.."""
+    for dtype, under_ff, under_00 in INT_POISON:
+        assert under_ff != under_00
+        for expected in (under_ff, under_00, 1 if dtype is not torch.bool else True):
+            seen = [GuardedArena(G, payload=p).alloc((1,), 'cpu', dtype)[0].item() for p in (0xFF, 0x00)]
+            assert any(v != expected for v in seen), (dtype, expected, seen)
+
+
+@pytest.mark.parametrize('payload', [0xFF, 0x00])
+def test_one_byte_past_a_uint8_payload_is_reported_under_either_payload(monkeypatch, payload):
+    from emsanet_amd import functional as Fn
+    a = GuardedArena(G, payload=payload)
+    install(monkeypatch, a)
+
+    def fake_wrapper():
+        return Fn._empty((5, 3), 'cpu', torch.uint8)
+    t = fake_wrapper()
+    buf, off, nbytes = _buffer_of(a)
+    assert nbytes == 15
+    buf[off:off + nbytes + 1] = 7                        # "the kernel" writes 16 labels into 15
+    with pytest.raises(GuardError) as e:
+        a.check()
+    msg = str(e.value)
+    assert re.search(r'test_guard\.py:fake_wrapper:\d+ shape \(5, 3\) torch\.uint8: rear band damaged, '
+                     r'first byte at offset 0 \(payload end \+ 0\), 1 bytes', msg), msg
+    assert 'front band' not in msg
+    del t
+
+
+@pytest.mark.parametrize('payload', [0xFF, 0x00])
+@pytest.mark.parametrize('dtype', [torch.float32, torch.int64, torch.int32, torch.uint8, torch.bool])
+def test_zeros_is_zero_under_either_payload(payload, dtype):
+    a = GuardedArena(G, payload=payload)
+    z = a.zeros((4, 9), 'cpu', dtype)
+    assert z.dtype == dtype and bool((z == 0).all())
+    buf, off, nbytes = _buffer_of(a)
+    assert bool((buf[:off] == 0xFF).all()) and bool((buf[off + nbytes:] == 0xFF).all())
+    assert a.check() == 1
+
+
+def test_put_is_the_same_under_either_payload():
+    for payload in (0xFF, 0x00):
+        a = GuardedArena(G, payload=payload)
+        v = torch.arange(11, dtype=torch.uint8)
+        g = a.put(v)
+        assert torch.equal(g, v)
+        buf, off, nbytes = _buffer_of(a)
+        assert bool((buf[:off] == 0xFF).all()) and bool((buf[off + nbytes:] == 0xFF).all())
+        a.check()
+
+
+# -- twins: the 0x00 run of a module whose tests keep their names ----------------------------------------
+_TWIN_SOURCE = '''
+import pytest
+from os.path import join as test_imported            # not of this module: no twin
+
+def helper():
+    return 0
+
+@pytest.mark.parametrize('a', [1, 2])
+@pytest.mark.usefixtures('tmp_path')
+def test_one(a, b=3, *, c=4):
+    """doc"""
+    return a + b + c
+
+def test_training_step_on_an_augmented_batch():       # opted out in guard.OPT_OUT
+    return 0
+'''
+
+
+def test_second_payload_adds_a_twin_per_test_with_its_marks():
+    import guard
+    ns = {'__file__': '/somewhere/test_augment_gpu.py', '__name__': 'twin_source'}
+    exec(_TWIN_SOURCE, ns)
+    before = set(ns)
+    assert guard.second_payload(ns) == ['test_one_poison00']
+    assert set(ns) - before == {'test_one_poison00'}
+    one, twin = ns['test_one'], ns['test_one_poison00']
+    assert twin is not one and twin.__name__ == twin.__qualname__ == 'test_one_poison00'
+    assert twin.__code__ is one.__code__ and twin.__doc__ == 'doc' and twin(1) == one(1) == 8
+    assert [m.name for m in twin.pytestmark] == [m.name for m in one.pytestmark] == ['usefixtures', 'parametrize']
+    assert twin.pytestmark is not one.pytestmark
+    assert guard.second_payload(ns) == []                # twins get no twins
+
+
+class _Node:
+    def __init__(self, name):
+        self.fspath, self.originalname, self.name = '/somewhere/test_augment_gpu.py', name, name + '[x]'
+
+
+class _Request:
+    def __init__(self, name):
+        self.node = _Node(name)
+
+
+@pytest.mark.parametrize('name, payload', [('test_one', 0xFF), ('test_one_poison00', 0x00)])
+def test_fixture_gives_a_twin_the_zero_payload(monkeypatch, capsys, name, payload):
+    import guard
+    from emsanet_amd import functional as Fn
+    gen = guard._guarded(_Request(name), monkeypatch, 0xFF)
+    arena = next(gen)
+    assert arena.payload == payload and guard._ACTIVE[-1] is arena
+    want = {0xFF: -1, 0x00: 0}[payload]
+    assert bool((Fn._empty((5,), 'cpu', torch.int32) == want).all())
+    assert bool((guard.put(torch.arange(3)) == torch.arange(3)).all()) and guard.check() == 2
+    with pytest.raises(StopIteration):
+        next(gen)
+    assert arena not in guard._ACTIVE and 'GUARD_COUNT test_augment_gpu.py' in capsys.readouterr().out
+
+
+@pytest.mark.parametrize('suffix', ['', '_poison00'])
+def test_fixture_leaves_an_opted_out_test_and_its_name_sake_alone(monkeypatch, suffix):
+    import guard
+    from emsanet_amd import functional as Fn
+    gen = guard._guarded(_Request('test_training_step_on_an_augmented_batch' + suffix), monkeypatch, 0xFF)
+    assert next(gen) is None and Fn._empty.__name__ == '_empty' and guard.put(None) is None

@@ -2,7 +2,13 @@
 NumPy reference of tests/test_metrics.py.  Counts are integers and must match exactly; iou_sum is
 int64 fixed point (2^-40), each term rounded once: |dev - ref| <= tp * 2^-40 per category (half a
 unit per term, with a factor 2 of margin); the nine results within 1e-9, the bar the reference sets
-its own metric against panopticapi (/root/reference/emsanet/tests/test_metrics_with_model.py:209-237)."""
+its own metric against panopticapi (/root/reference/emsanet/tests/test_metrics_with_model.py:209-237).
+
+Every test runs on the guarded arena of tests/guard.py, once per payload byte -- as
+`test_x` on 0xFF and as its twin `test_x_poison00` on 0x00 -- (all counts are integers
+compared exactly): the state vectors, the hash-table workspace and the match tables lie between two
+bands of 0xFF -- the confusion matrix is binned by `target * C + pred`, data the kernel reads -- and
+the prediction and label maps are placed with `guard.put`."""
 import os
 import sys
 from fractions import Fraction
@@ -12,7 +18,9 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import guard   # noqa: E402
 import test_metrics as R   # noqa: E402
+from guard import guard_allocations  # noqa: E402,F401  (autouse: poisoned, guard-banded allocations)
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -43,8 +51,8 @@ def test_confusion_matrix_and_miou(c, shape, dt_pred, dt_target, ignore_first):
     from emsanet_amd import MeanIntersectionOverUnion
     pred, target = _label_maps(c, shape, seed=c)
     m = MeanIntersectionOverUnion(c, ignore_first_class=ignore_first)
-    m.update(torch.from_numpy(pred.astype(NP_DTYPES[dt_pred])).to(DEV),
-             torch.from_numpy(target.astype(NP_DTYPES[dt_target])).to(DEV))
+    m.update(_dev(pred.astype(NP_DTYPES[dt_pred])), _dev(target.astype(NP_DTYPES[dt_target])))
+    guard.check()
     cm, bad = R.confusion_reference(pred, target, c)
     assert bad == 0 and cm.sum() == pred.size
     got = m.confusion_matrix
@@ -52,8 +60,7 @@ def test_confusion_matrix_and_miou(c, shape, dt_pred, dt_target, ignore_first):
     assert np.array_equal(got.cpu().numpy(), cm)
     assert abs(m.compute() - R.miou_reference(cm, ignore_first)) <= 1e-12
     # a second update accumulates, reset clears
-    m.update(torch.from_numpy(pred.astype(NP_DTYPES[dt_pred])).to(DEV),
-             torch.from_numpy(target.astype(NP_DTYPES[dt_target])).to(DEV))
+    m.update(_dev(pred.astype(NP_DTYPES[dt_pred])), _dev(target.astype(NP_DTYPES[dt_target])))
     assert np.array_equal(m.confusion_matrix.cpu().numpy(), 2 * cm)
     m.reset()
     assert int(m.confusion_matrix.abs().sum()) == 0
@@ -69,15 +76,36 @@ def test_confusion_matrix_label_out_of_range(c, shape, side):
     pred, target = _label_maps(c, shape, seed=7)
     (pred if side == 'pred' else target)[-1, -1, -1] = c
     m = MeanIntersectionOverUnion(c)
-    m.update(torch.from_numpy(pred).to(DEV), torch.from_numpy(target).to(DEV))
+    m.update(_dev(pred), _dev(target))
+    guard.check()
     cm, bad = R.confusion_reference(pred, target, c)
     assert bad == 1 and cm.sum() == pred.size - 1
     assert np.array_equal(m.confusion_matrix.cpu().numpy(), cm)
     with pytest.raises(ValueError, match='n_invalid'):
         m.compute()
     m.reset()
-    m.update(torch.from_numpy(np.minimum(pred, c - 1)).to(DEV), torch.from_numpy(np.minimum(target, c - 1)).to(DEV))
+    m.update(_dev(np.minimum(pred, c - 1)), _dev(np.minimum(target, c - 1)))
     assert m.compute() > 0
+
+
+@pytest.mark.parametrize('c,shape,dtype', [(5, (2, 37, 53), torch.uint8), (5, (1, 1, 1), torch.int64),
+                                           (200, (2, 15, 13), torch.uint8), (200, (1, 48, 64), torch.int32)])
+def test_confusion_matrix_last_bin_from_the_last_pixel(c, shape, dtype):
+    """the last pixel of the last image carries (C - 1, C - 1): the last input element goes into the
+    last bin of the matrix, at the small class count (LDS bins) and at 200 (global atomics; 199 as
+    uint8 is above 127).  n_invalid, right behind the matrix, stays 0"""
+    from emsanet_amd import MeanIntersectionOverUnion
+    pred, target = _label_maps(c, shape, seed=c + 1)
+    pred[...] = np.minimum(pred, c - 2)              # so that the last bin is that pixel's alone
+    pred[-1, -1, -1] = target[-1, -1, -1] = c - 1
+    m = MeanIntersectionOverUnion(c)
+    m.update(_dev(pred.astype(NP_DTYPES[dtype])), _dev(target.astype(NP_DTYPES[dtype])))
+    guard.check()
+    cm, bad = R.confusion_reference(pred, target, c)
+    assert bad == 0 and cm[c - 1, c - 1] == 1 and cm.sum() == pred.size
+    assert np.array_equal(m.confusion_matrix.cpu().numpy(), cm)
+    assert int(m._state[-1]) == 0
+    assert abs(m.compute() - R.miou_reference(cm, False)) <= 1e-12
 
 
 # ---- panoptic quality ---------------------------------------------------------------------------
@@ -114,7 +142,7 @@ def _scene(name):
 
 
 def _dev(a):
-    return torch.from_numpy(a).to(DEV)
+    return guard.put(torch.from_numpy(a).to(DEV))    # flush between two bands of 0xFF
 
 
 def _assert_matches(metric, ref, what=''):
@@ -140,6 +168,7 @@ def test_panoptic_quality_random_scenes(name):
         assert min(sum(one.tp), sum(one.fp), sum(one.fn), one.void_skipped) >= 1
     m = _pq(div)
     m.update(_dev(pred), _dev(target))
+    guard.check()
     _assert_matches(m, ref, name)
 
 
@@ -207,6 +236,7 @@ def test_updates_capture_into_a_graph():
     assert int(once_pq[:-1].abs().sum()) > 0 and int(once_cm.sum()) == pred.size
     assert torch.equal(pq._state, 3 * once_pq)          # (the flag word is 0)
     assert torch.equal(miou._state, 3 * once_cm)
+    guard.check()                                       # (state and workspace were made by the warm-up calls)
 
 
 def test_panoptic_quality_segment_table_overflow():
@@ -217,6 +247,7 @@ def test_panoptic_quality_segment_table_overflow():
     crowded = (4 * div + grid).astype(np.int64)[None]
     m = _pq(div, max_segments=8)
     m.update(_dev(crowded), _dev(crowded))
+    guard.check()                                       # the twelve segments too many were stored nowhere
     with pytest.raises(ValueError, match='overflow'):
         m.compute()
     m.reset()
@@ -227,6 +258,7 @@ def test_panoptic_quality_segment_table_overflow():
     few = (4 * div + (grid - 1) % 8).astype(np.int64)[None]
     m.reset()
     m.update(_dev(few), _dev(few))
+    guard.check()
     assert m.counts()['tp'][4] == 8 and m.compute()['all_pq'] == 1.0
 
 
@@ -303,3 +335,7 @@ def test_validation_loop_end_to_end():
     assert sum(ref.tp) >= 1 and sum(ref.fn) >= 1
     _assert_matches(pq, ref, 'end to end')
     assert pq.compute()['all_pq'] > 0 and miou.compute() > 0
+
+
+# every test above once more as `<name>_poison00`, on 0x00 payloads (True, 255 and -1 are legal values)
+guard.second_payload(globals())

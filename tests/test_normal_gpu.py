@@ -6,7 +6,12 @@ error <= 1e-5 * max |reference| + 1e-12, against fp64 on the fp32 values the ker
 augmentation are copies: bit-equal; unit vectors |d| <= 1e-6 per component against F.normalize on the CPU
 (components are at most 1, a handful of fp32 roundings of at most 6e-8 each); the metric's count is exact
 and its mean within 1e-5 rad of the float64 reference (fp32 cross / dot / atan2: order 3e-6 at angles up
-to pi, plus the 2^-21 rad of the fixed point).  Every comparison prints its figures before it asserts."""
+to pi, plus the 2^-21 rad of the fixed point).  Every comparison prints its figures before it asserts.
+
+Every test but the two whole-model ones runs on the guarded arena of tests/guard.py (payload 0xFF = NaN:
+the compared outputs are floating point): target and augmentation ring slots, the unit vectors and the
+metric state lie between two bands of 0xFF, and normal maps, predictions and parameter rows are placed
+with `guard.put`."""
 import math
 import os
 import sys
@@ -16,8 +21,10 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import guard   # noqa: E402
 import normal_reference as R   # noqa: E402
 import targets_reference as T   # noqa: E402
+from guard import guard_allocations  # noqa: E402,F401  (autouse: poisoned, guard-banded allocations)
 from util import DEV, deterministic_state_dict   # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -31,7 +38,7 @@ _CACHE = {}
 
 
 def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    return guard.put(torch.from_numpy(np.ascontiguousarray(a)).to(DEV))    # flush between two bands of 0xFF
 
 
 def _target(hwc, layout):
@@ -187,6 +194,7 @@ def test_targets_equal_the_reference(layout):
     gen = _generator()
     batch = {'semantic': torch.zeros(2, 96, 128, dtype=torch.uint8, device=DEV), 'normal': _target(t, layout)}
     got = gen.generate(batch)
+    guard.check()
     assert sorted(got) == ['normal', 'semantic']
     _assert_targets(got['normal'], ref)
     first = [g.data_ptr() for g in got['normal']]
@@ -228,6 +236,7 @@ def test_targets_capture_into_a_graph():
     torch.cuda.synchronize()
     for g, e in zip(got, eager):
         assert torch.equal(g, e)
+    guard.check()                                          # (both ring slots were made before the capture)
 
 
 def test_targets_refuse_a_bad_normal_map():
@@ -288,6 +297,7 @@ def test_augment_explicit_rows(layout):
     batch, t = _raw_batch(4, layout)
     aug = _augmenter()
     out = aug.apply(batch, params=_dev(table))
+    guard.check()
     assert sorted(out) == ['depth', 'normal', 'rgb', 'semantic']
     g = _assert_augmented(out['normal'], t, table, f'explicit rows, {layout}')
     assert np.array_equal(g[0], t[0, :H, :W])
@@ -334,6 +344,7 @@ def test_unit_vectors(shape, dense):
         pred = pred.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)       # ld = 3: scalar loads
     prediction = {'normal_output': pred, 'normal_side_outputs': ()}
     out = NormalPostprocessing()(prediction)
+    guard.check()
     assert out is prediction and sorted(out) == ['normal_output', 'normal_side_outputs', 'normal_vectors']
     v = out['normal_vectors']
     assert v.dtype == torch.float32 and tuple(v.shape) == shape and v.permute(0, 2, 3, 1).is_contiguous()
@@ -409,6 +420,7 @@ def test_metric_with_a_target_twice_the_size():
     assert t.shape == (2, 30, 40, 3)
     m = MeanAbsoluteNormalError()
     m.update(_pred_dev(p), _dev(t))
+    guard.check()
     _check_metric(m, [(p, t)], 'target 2x')
     dense = MeanAbsoluteNormalError()                        # a dense ld = 3 prediction: scalar loads
     dense.update(_dev(np.moveaxis(p, 1, -1)).permute(0, 3, 1, 2), _dev(t))

@@ -175,3 +175,19 @@ def test_sum_oracles_agree_with_the_dictionary_oracles(slots):
             assert a == int(area[i, k])
             import numpy as np
             assert mean == float(np.float32(float(ssum[i, k]) / float(a) / 2.0 ** 30))
+
+
+def test_cap_heat_fills_the_candidate_lists_exactly():
+    heat = C.cap_heat()
+    k = C.CAP_TOP_K
+    assert heat.shape == (3, 1, 33, 64) and -(-33 * 64 // C.CHUNK) == 3           # cap = 3 * top_k
+    _, keep = O.center_keep_mask(heat, 0.1, 1)
+    assert keep.reshape(3, -1).sum(1).tolist() == [3 * k, 3 * k + 1, k]
+    assert C.merge_candidates(heat, 0.1, 1, k).tolist() == [3 * k, 3 * k, k]
+    ref = O.instance_centers(heat, 0.1, 1, k)
+    assert [len(r[0]) for r in ref] == [k, k, k]
+    vals = heat[heat > 0]
+    assert vals.unique().numel() == vals.numel() == 7 * k + 1 and float(vals.min()) >= 0.2
+    # the survivor that image 1 loses to the cap is the lowest of its first chunk: not among the top k
+    first = heat[1, 0].view(-1)[:C.CHUNK]
+    assert float(first[first > 0].min()) < float(ref[1][1].min())

@@ -5,7 +5,13 @@ grid-stride loops of every capped launch, the LDS / global switch of the per-ins
 constructed panoptic-merge cases, the full input range of the normalisation, and the dtype contract of
 the Python wrappers.  References: oracle/postprocessing_oracle.py (fp64 where arithmetic matters) or
 torch itself; the inputs are built in tests/postprocessing_cases.py, whose claimed properties
-tests/test_postprocessing_edges.py checks without a device."""
+tests/test_postprocessing_edges.py checks without a device.
+
+Every test runs on the guarded arena of tests/guard.py, once per payload byte -- as
+`test_x` on 0xFF and as its twin `test_x_poison00` on 0x00 -- (index maps, ids, areas,
+integer sums and the -1 padding of the centre lists are compared exactly, and -1 is what 0xFF reads
+as): outputs and the integer work buffers -- candidate lists of n * cap entries, votes of
+(top_k + 1) * nc, per-slot sums -- lie between two bands of 0xFF; inputs are placed with `_d`."""
 import os
 import sys
 
@@ -15,11 +21,17 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import postprocessing_cases as C   # noqa: E402
+import guard   # noqa: E402
 from guard import guard_allocations  # noqa: E402,F401  (autouse: poisoned, guard-banded allocations)
 from oracle import postprocessing_oracle as O   # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
+
+
+def _d(t):
+    """`t` on the device, flush between two bands of 0xFF"""
+    return guard.put(t.to(DEV))
 
 
 def _err():
@@ -30,11 +42,12 @@ def _err():
 # ---- 1. centres --------------------------------------------------------------------------------
 def _check_centers(heat, threshold, kernel, top_k, fg=None, twice=True):
     from emsanet_amd.postprocessing import instance_centers
-    dfg = None if fg is None else fg.to(DEV)
-    c1, s1, n1, surv = instance_centers(heat.to(DEV), threshold, kernel, top_k, dfg, return_survivors=True)
+    dfg = None if fg is None else _d(fg)
+    c1, s1, n1, surv = instance_centers(_d(heat), threshold, kernel, top_k, dfg, return_survivors=True)
     if twice:
-        c2, s2, n2 = instance_centers(heat.to(DEV), threshold, kernel, top_k, dfg)
+        c2, s2, n2 = instance_centers(_d(heat), threshold, kernel, top_k, dfg)
         assert torch.equal(c1, c2) and torch.equal(s1, s2) and torch.equal(n1, n2)   # reproducible
+    guard.check()
     ref = O.instance_centers(heat, threshold, kernel, top_k, fg)
     _, keep = O.center_keep_mask(heat, threshold, kernel, fg)
     assert surv.cpu().tolist() == keep.reshape(keep.shape[0], -1).sum(1).tolist()
@@ -72,6 +85,18 @@ def test_center_topk_merge_in_rounds_default_parameters(case):
     heat = C.default_heat(case)
     _, _, n1, _ = _check_centers(heat, 0.1, 17, 64)
     assert n1.cpu().tolist() == [64] * 2
+
+
+def test_center_candidate_lists_exactly_full_and_one_over():
+    """33 x 64, top_k 8: cap = 24 candidates per image.  Image 0 hands in exactly 24, image 1 has a ninth
+    survivor in its first chunk, which is cut, image 2 has exactly top_k survivors: all eight centre
+    slots used, none padded (tests/test_postprocessing_edges.py: the heat map's claims)"""
+    from emsanet_amd import _lib
+    heat, k = C.cap_heat(), C.CAP_TOP_K
+    assert _lib.lib().emsa_center_ws_entries(33, 64, k) == 3 * k
+    c1, s1, n1, _ = _check_centers(heat, 0.1, 1, k)
+    assert n1.cpu().tolist() == [k] * 3
+    assert bool((c1 >= 0).all()) and bool((s1 >= 0.2).all())
 
 
 @pytest.mark.parametrize('kernel', [3, 31])
@@ -120,7 +145,7 @@ def test_center_score_edges():
 # ---- 2. assignment -----------------------------------------------------------------------------
 def _assign(off, centers, nc, fg, normalized, dist):
     from emsanet_amd.postprocessing import instance_assign
-    return instance_assign(off.to(DEV), centers.to(DEV), nc.to(DEV), None if fg is None else fg.to(DEV),
+    return instance_assign(_d(off), _d(centers), _d(nc), None if fg is None else _d(fg),
                            normalized, dist).cpu()
 
 
@@ -158,6 +183,7 @@ def test_assignment_small_edges(normalized):
     nc = torch.tensor([512, 0], dtype=torch.int32)
     for fg, dist in ((None, None), (mask, 6.0)):
         ids = _assign(off, centers, nc, fg, normalized, dist)
+        guard.check()
         assert int(ids[1].abs().max()) == 0                               # no centres: no instance
         assert int(ids[0].max()) > 256
         C.assign_check(ids, off, centers, nc, fg, normalized, dist, 1e-3 if dist else 1e-4)
@@ -170,7 +196,8 @@ def test_assignment_small_edges(normalized):
 # ---- 3. softmax / arg-max ----------------------------------------------------------------------
 def _check_softmax(x, dev_x=None):
     from emsanet_amd.postprocessing import softmax_argmax
-    score, idx = softmax_argmax(x.to(DEV) if dev_x is None else dev_x)
+    score, idx = softmax_argmax(_d(x) if dev_x is None else dev_x)
+    guard.check()
     rs, ri = O.softmax_argmax(x)
     assert idx.dtype == torch.int64 and score.dtype == torch.float32
     assert torch.equal(idx.cpu(), ri)
@@ -190,7 +217,7 @@ def test_softmax_argmax_class_counts(c):
         if c >= 6:
             x[0, 3, 0, 0] = x[0, 5, 0, 0] = 17.0                         # a tie: first maximum wins
         _check_softmax(x)
-        _check_softmax(x, x.to(DEV).contiguous(memory_format=torch.channels_last))
+        _check_softmax(x, _d(x).contiguous(memory_format=torch.channels_last))
 
 
 def test_softmax_argmax_refuses_65_classes():
@@ -209,10 +236,10 @@ def test_softmax_argmax_padded_view_ignores_the_pad_channels():
     buf = torch.empty(n, h, w, 40)
     buf[..., :c] = x.permute(0, 2, 3, 1)
     buf[..., 37], buf[..., 38], buf[..., 39] = float('inf'), float('nan'), 1e30
-    view = buf.to(DEV)[..., :c].permute(0, 3, 1, 2)
+    view = _d(buf)[..., :c].permute(0, 3, 1, 2)
     assert view.stride(3) == 40
     s1, i1 = _check_softmax(x, view)
-    s2, i2 = softmax_argmax(x.to(DEV))
+    s2, i2 = softmax_argmax(_d(x))
     assert torch.equal(s1, s2) and torch.equal(i1, i2)
 
 
@@ -253,7 +280,7 @@ def test_softmax_argmax_rows(n, c):
     from emsanet_amd.postprocessing import softmax_argmax
     g = torch.Generator().manual_seed(300 + n + c)
     x = torch.randn(n, c, generator=g) * 4
-    score, idx = softmax_argmax(x.to(DEV))
+    score, idx = softmax_argmax(_d(x))
     rs, ri = O.softmax_argmax(x)
     assert score.shape == idx.shape == (n,)
     assert torch.equal(idx.cpu(), ri) and (score.cpu().double() - rs).abs().max() <= 1e-6
@@ -265,12 +292,13 @@ def test_panoptic_merge_and_scores_on_a_batch_of_real_frames():
     stride (and the per-image stats grid does).  Bit-equal to the oracle, twice in a row"""
     from emsanet_amd.postprocessing import panoptic_merge, panoptic_scores
     sem, ids, score, cscore, ref_m, (rs, ri, rp, per) = C.big_panoptic()
-    dsem, dids, dscore, dcs = sem.to(DEV), ids.to(DEV), score.to(DEV), cscore.to(DEV)
+    dsem, dids, dscore, dcs = _d(sem), _d(ids), _d(score), _d(cscore)
     for _ in range(2):
         m = panoptic_merge(dsem, dids, C.IS_THING, top_k=C.TOP_K)
         for key in ('semantic', 'instance', 'panoptic', 'instance_class'):
             assert torch.equal(m[key].cpu(), ref_m[key].to(m[key].dtype)), key
         got = panoptic_scores(dscore, m['instance'], m['semantic'], dcs)
+        guard.check()
         assert torch.equal(got['semantic_score'].cpu(), rs)
         assert torch.equal(got['instance_score'].cpu(), ri)
         assert torch.equal(got['panoptic_score'].cpu(), rp)
@@ -288,15 +316,15 @@ def test_panoptic_merge_constructed_cases():
     for s in (sem, sem.flip(2)):            # the tie must not depend on which class is met first
         i = ids if s is sem else ids.flip(2)
         r = ref if s is sem else {k: (v.flip(2) if v.dim() == 3 else v) for k, v in ref.items()}
-        got = panoptic_merge(s.to(DEV), i.to(DEV), is_thing, top_k=top_k)
+        got = panoptic_merge(_d(s), _d(i), is_thing, top_k=top_k)
         for key in ('semantic', 'instance', 'panoptic', 'instance_class'):
             assert torch.equal(got[key].cpu(), r[key].to(got[key].dtype)), key
     assert got['instance_class'][0].cpu().tolist() == [-1, 3, -1, 4, 1]   # tie -> lower class; stuff -> -1
     # label_divisor <= top_k is refused
     with pytest.raises(_err()):
-        panoptic_merge(sem.to(DEV), ids.to(DEV), is_thing, top_k=top_k, label_divisor=top_k)
+        panoptic_merge(_d(sem), _d(ids), is_thing, top_k=top_k, label_divisor=top_k)
     torch.cuda.synchronize()
-    got = panoptic_merge(sem.to(DEV), ids.to(DEV), is_thing, top_k=top_k, label_divisor=top_k + 1)
+    got = panoptic_merge(_d(sem), _d(ids), is_thing, top_k=top_k, label_divisor=top_k + 1)
     ref = O.panoptic_merge(sem, ids, is_thing, label_divisor=top_k + 1, top_k=top_k)
     assert torch.equal(got['panoptic'].cpu(), ref['panoptic'])
 
@@ -307,14 +335,15 @@ def test_instance_sums_at_the_lds_switch(slots):
     from emsanet_amd.postprocessing import instance_orientation_sums, instance_stats
     ids, score, ori, mask = C.stats_case(slots)
     for mk in (None, mask):
-        dmk = None if mk is None else mk.to(DEV)
+        dmk = None if mk is None else _d(mk)
         ra, rsum = O.instance_sums(ids, slots, score, mk)
         rvec, rcnt = O.instance_orientation_sums(ori, ids, slots, mk)
         for _ in range(2):
-            area, ssum = instance_stats(ids.to(DEV), slots, score.to(DEV), dmk)
+            area, ssum = instance_stats(_d(ids), slots, _d(score), dmk)
             assert torch.equal(area.cpu().long(), ra) and torch.equal(ssum.cpu(), rsum)
-            assert torch.equal(instance_stats(ids.to(DEV), slots, None, dmk).cpu().long(), ra)
-            vec, cnt = instance_orientation_sums(ori.to(DEV), ids.to(DEV), slots, dmk)
+            assert torch.equal(instance_stats(_d(ids), slots, None, dmk).cpu().long(), ra)
+            vec, cnt = instance_orientation_sums(_d(ori), _d(ids), slots, dmk)
+            guard.check()
             assert torch.equal(vec.cpu(), rvec) and torch.equal(cnt.cpu().long(), rcnt)
     assert int(ra[:, slots - 1].min()) > 0
 
@@ -323,7 +352,7 @@ def test_instance_sums_at_the_lds_switch(slots):
 def test_normalize_rgb_full_range_batch_of_real_frames():
     from emsanet_amd.postprocessing import RGB_MEAN, RGB_STD, normalize_rgb
     rgb, _ = C.big_frames()
-    drgb = rgb.to(DEV)
+    drgb = _d(rgb)
     for mean, std, scale in ((RGB_MEAN, RGB_STD, 1.0 / 255.0), ((100.0, 110.0, 120.0), (50.0, 60.0, 70.0), 1.0)):
         out = normalize_rgb(drgb, mean, std, scale).cpu()
         ref = ((rgb.double() * scale - torch.tensor(mean, dtype=torch.float64)) /
@@ -347,7 +376,7 @@ def test_normalize_depth_full_range_batch_of_real_frames(keep_zero):
     d16 = torch.from_numpy(depth.numpy().astype(np.uint16).view(np.int16))
     assert int(d16.min()) < 0
     for mean, std in ((2841.9, 1417.3), (1000.0, -250.5)):
-        out = normalize_depth(d16.to(DEV), mean, std, keep_zero).cpu()
+        out = normalize_depth(_d(d16), mean, std, keep_zero).cpu()
         ref = (depth.double() - mean) / std
         if keep_zero:
             ref[depth == 0] = 0.0
@@ -405,7 +434,7 @@ def test_integer_inputs_are_converted_to_the_width_the_kernels_read():
     score = torch.rand(n, h, w, generator=g)
     cscore = torch.rand(n, k, generator=g)
     ori = torch.randn(n, 2, h, w, generator=g)
-    dsem, dids = sem.to(DEV), ids.to(DEV)                                 # both int64
+    dsem, dids = _d(sem), _d(ids)                                 # both int64
     good = panoptic_merge(dsem, dids.int(), is_thing, top_k=k)
     ref = O.panoptic_merge(sem, ids.int(), is_thing, top_k=k)
     assert torch.equal(good['panoptic'].cpu(), ref['panoptic'])
@@ -413,19 +442,19 @@ def test_integer_inputs_are_converted_to_the_width_the_kernels_read():
         got = panoptic_merge(s, i, is_thing, top_k=k)
         for key in good:
             assert torch.equal(got[key], good[key]), (s.dtype, i.dtype, key)
-    a, ss = instance_stats(dids.int(), k + 1, score.to(DEV))
+    a, ss = instance_stats(dids.int(), k + 1, _d(score))
     ra, rsum = O.instance_sums(ids, k + 1, score)
     assert torch.equal(a.cpu().long(), ra) and torch.equal(ss.cpu(), rsum)
-    for i, v in ((dids, score.to(DEV)), (dids.int(), score.double().to(DEV)), (dids.short(), score.to(DEV))):
+    for i, v in ((dids, _d(score)), (dids.int(), score.double().to(DEV)), (dids.short(), _d(score))):
         a2, s2 = instance_stats(i, k + 1, v)
         assert torch.equal(a2, a) and torch.equal(s2, ss)
-    v1 = instance_orientation_sums(ori.to(DEV), dids.int(), k + 1)
-    v2 = instance_orientation_sums(ori.to(DEV), dids, k + 1)
+    v1 = instance_orientation_sums(_d(ori), dids.int(), k + 1)
+    v2 = instance_orientation_sums(_d(ori), dids, k + 1)
     assert torch.equal(v1[0], v2[0]) and torch.equal(v1[1], v2[1])
-    p1 = panoptic_scores(score.to(DEV), good['instance'], good['semantic'], cscore.to(DEV))
+    p1 = panoptic_scores(_d(score), good['instance'], good['semantic'], _d(cscore))
     p2 = panoptic_scores(score.double().to(DEV), good['instance'].long(), good['semantic'].int(),
                          cscore.half().to(DEV))
-    p3 = panoptic_scores(score.to(DEV), good['instance'], good['semantic'], cscore.half().float().to(DEV))
+    p3 = panoptic_scores(_d(score), good['instance'], good['semantic'], cscore.half().float().to(DEV))
     assert torch.equal(p1['semantic_score'], p2['semantic_score']) and torch.equal(p1['area'], p2['area'])
     for key in p3:
         assert torch.equal(p2[key], p3[key]), key
@@ -462,19 +491,23 @@ def test_host_tensors_are_refused():
              lambda: P.instance_assign(x[:, :2], cen, nc),
              lambda: P.instance_assign(dev_off, cen.cpu(), nc),
              lambda: P.instance_assign(dev_off, cen, nc.cpu()),
-             lambda: P.panoptic_merge(sem, ids.to(DEV), [True, False]),
-             lambda: P.panoptic_merge(sem.to(DEV), ids, [True, False]),
+             lambda: P.panoptic_merge(sem, _d(ids), [True, False]),
+             lambda: P.panoptic_merge(_d(sem), ids, [True, False]),
              lambda: P.instance_stats(ids, 5),
-             lambda: P.instance_stats(ids.to(DEV), 5, x[:, 0]),
-             lambda: P.instance_stats(ids.to(DEV), 5, None, sem),
-             lambda: P.panoptic_scores(x[:, 0], ids.to(DEV), sem.to(DEV), sc),
-             lambda: P.panoptic_scores(x[:, 0].to(DEV), ids, sem.to(DEV), sc),
-             lambda: P.panoptic_scores(x[:, 0].to(DEV), ids.to(DEV), sem, sc),
-             lambda: P.panoptic_scores(x[:, 0].to(DEV), ids.to(DEV), sem.to(DEV), sc.cpu()),
-             lambda: P.instance_orientation_sums(x[:, :2], ids.to(DEV), 5),
+             lambda: P.instance_stats(_d(ids), 5, x[:, 0]),
+             lambda: P.instance_stats(_d(ids), 5, None, sem),
+             lambda: P.panoptic_scores(x[:, 0], _d(ids), _d(sem), sc),
+             lambda: P.panoptic_scores(x[:, 0].to(DEV), ids, _d(sem), sc),
+             lambda: P.panoptic_scores(x[:, 0].to(DEV), _d(ids), sem, sc),
+             lambda: P.panoptic_scores(x[:, 0].to(DEV), _d(ids), _d(sem), sc.cpu()),
+             lambda: P.instance_orientation_sums(x[:, :2], _d(ids), 5),
              lambda: P.instance_orientation_sums(x[:, :2].to(DEV), ids, 5)]
     for j, call in enumerate(calls):
         with pytest.raises(E):
             call()
             pytest.fail(f"call {j} accepted a host tensor")
     torch.cuda.synchronize()
+
+
+# every test above once more as `<name>_poison00`, on 0x00 payloads (True, 255 and -1 are legal values)
+guard.second_payload(globals())

@@ -198,3 +198,20 @@ def test_c_abi_rejects_bad_geometry_before_any_launch():
                                  None, None, None) == -1                            # max_instances
     sc[0].center, sc[0].sigma = 4096, 0
     assert L.emsa_targets_stats(None, 0, None, 0, None, 6, 1, 96, 128, sc, 1, 256, None, None) == -1   # sigma 0
+
+
+def test_corner_scene_holds_its_cases():
+    sem, inst, ori, scene = R.corner_scene()
+    r = R.reference_targets(sem, inst, R.IS_THING, R.USE_ORIENTATION, ori, scene)
+    assert [t.shape[1:] for t in r['semantic']] == [(32, 32), (1, 1), (2, 2), (4, 4)]
+    assert all(t[0].size % 64 for t in r['semantic'][1:])
+    # the four corners at full scale, the last table entry among them; the side scales sample (0, 0) only
+    assert r['centers'][0][0] == {1: (1, 1), 2: (1, 30), 254: (30, 1), 255: (30, 30)}
+    assert [c[0] for c in r['centers'][1:]] == [{1: (0, 0)}] * 3
+    assert [c[1] for c in r['centers']] == [{255: (16, 16)}, {255: (0, 0)}, {255: (0, 0)}, {255: (2, 2)}]
+    c = r['instance'][0]['center'][0, 0]
+    for y, x in ((0, 0), (0, 31), (31, 0), (31, 31)):       # the window (radius 25) leaves the image there
+        assert 0 < c[y, x] < 1
+    assert c[1, 1] == c[1, 30] == c[30, 1] == c[30, 30] == 1.0
+    assert r['instance'][1]['center'].shape == (2, 1, 1, 1) and (r['instance'][1]['center'] == 1.0).all()
+    assert not r['bad_id'] and not r['bad_label']

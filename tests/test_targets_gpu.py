@@ -11,7 +11,12 @@ image without any instance; non-contiguous ids including max_instances - 1; a on
 instance touching two borders (clipped window); two instances whose windows overlap (the maximum); an
 instance on a stuff class and one on void (both cleared); an instance that vanishes at /32; a mean of
 exactly x.5 in both directions with an even and with an odd integer part; orientations present, NaN,
-and on a class that uses none -- tests/test_targets.py checks that it does."""
+and on a class that uses none -- tests/test_targets.py checks that it does.
+
+Every test runs on the guarded arena of tests/guard.py, once per payload byte -- as
+`test_x` on 0xFF and as its twin `test_x_poison00` on 0x00 -- (the label maps, both
+bool masks and the centre table are compared exactly, and True / -1 are what 0xFF reads as): outputs,
+ring slots and the workspace lie between two bands of 0xFF, the inputs are placed with `guard.put`."""
 import os
 import sys
 
@@ -20,7 +25,9 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import guard   # noqa: E402
 import targets_reference as R   # noqa: E402
+from guard import guard_allocations  # noqa: E402,F401  (autouse: poisoned, guard-banded allocations)
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -40,7 +47,7 @@ def _gen(args=None, **kw):
 
 def _dev(a, dtype=None):
     t = torch.from_numpy(np.ascontiguousarray(a if dtype is None else a.astype(NP_DTYPES[dtype])))
-    return t.to(DEV)
+    return guard.put(t.to(DEV))                  # flush between two bands of 0xFF: a read past its end is poison
 
 
 def _batch(sem, inst, ori=None, scene=None, dt_sem=None, dt_inst=None):
@@ -105,8 +112,50 @@ def test_edge_scene_every_label_dtype(edge, dt_sem, dt_inst):
     gen = _gen()
     got = gen.generate(_batch(sem, inst, ori, scene, dt_sem, dt_inst))
     gen.check()
+    guard.check()
     assert got.get('center_mask') is None
     assert_targets(got, ref, centers=gen.last_centers())
+
+
+@pytest.fixture(scope='module')
+def corner():
+    sem, inst, ori, scene = R.corner_scene()
+    return sem, inst, ori, scene, R.reference_targets(sem, inst, R.IS_THING, R.USE_ORIENTATION, ori, scene)
+
+
+@pytest.mark.parametrize('dt_sem, dt_inst', [(torch.uint8, torch.uint8), (torch.int64, torch.int16),
+                                             (torch.int32, torch.int64)])
+def test_corner_scene_one_pixel_scale_maps(corner, dt_sem, dt_inst):
+    """32x32: scale maps of 1x1, 2x2 and 4x4 pixels (1, 4, 16: no multiple of 64, one partial wave),
+    Gaussian windows clipped at each of the four image corners, the last id of the table in the last
+    pixel of image 0 and as the only instance of image 1 (tests/test_targets.py: the scene's claims)"""
+    sem, inst, ori, scene, ref = corner
+    gen = _gen()
+    got = gen.generate(_batch(sem, inst, ori, scene, dt_sem, dt_inst))
+    gen.check()
+    guard.check()
+    assert [tuple(t.shape[1:]) for t in got['semantic']] == [(32, 32), (1, 1), (2, 2), (4, 4)]
+    assert_targets(got, ref, centers=gen.last_centers())
+
+
+def test_last_table_entry_beside_the_first_refused_id(corner):
+    """max_instances = 200 on the corner scene with its ids moved: 199, the last entry of every
+    per-instance table (acc[3][m], the list, centre_of), is stored; 200, on its neighbour pixels, is
+    flagged and stored nowhere -- the guards stand behind each table"""
+    sem, inst, ori, scene, _ = corner
+    m = 200
+    inst = np.where(inst == 255, m - 1, np.where(inst == 254, m, inst))
+    assert (inst[0, 29:, 29:] == m - 1).all() and (inst[0, 29:, :3] == m).all() and (inst[1] == m - 1).all()
+    ori = np.ascontiguousarray(ori[:, :m])
+    ori[:, m - 1] = 0.5
+    ref = R.reference_targets(sem, inst, R.IS_THING, R.USE_ORIENTATION, ori, scene, max_instances=m)
+    assert ref['bad_id'] and ref['centers'][0][0] == {1: (1, 1), 2: (1, 30), m - 1: (30, 30)}
+    gen = _gen(max_instances=m)
+    got = gen.generate(_batch(sem, inst, ori, scene, torch.uint8, torch.uint8))
+    guard.check()
+    assert_targets(got, ref, centers=gen.last_centers())
+    with pytest.raises(ValueError, match='instance id'):
+        gen.check()
 
 
 def test_large_instance_and_many_small_ones():
@@ -120,6 +169,7 @@ def test_large_instance_and_many_small_ones():
     batch = _batch(sem, inst, dt_sem=torch.uint8, dt_inst=torch.int32)
     first = gen.generate(batch)
     assert_targets(first, ref, centers=gen.last_centers())
+    guard.check()
     second = gen.generate(batch)                     # the other ring slot: `first` stays valid
     gen.check()
     for a, b in zip(first['instance'], second['instance']):
@@ -216,6 +266,7 @@ def test_error_flag(edge, what):
     gen = _gen()
     gen.check()
     got = gen.generate(_batch(sem, inst, ori, scene, dt_inst=torch.int32))
+    guard.check()
     assert_targets(got, bad, centers=gen.last_centers())
     with pytest.raises(ValueError, match='instance id' if what == 'id' else 'semantic label'):
         gen.check()
@@ -261,6 +312,7 @@ def test_generate_captures_into_a_graph(edge):
         batch[key].copy_(_dev(new).to(batch[key].dtype))
     graph.replay()
     torch.cuda.synchronize()
+    guard.check()                                    # (every buffer was made by the warm-up call, before the capture)
     assert_targets(got, ref2, centers=gen.last_centers())
     batch['semantic'].copy_(_dev(sem).to(torch.uint8))
     batch['instance'].copy_(_dev(inst).to(torch.int32))
@@ -348,9 +400,14 @@ def test_batch_stager_hands_out_targets(edge):
     staged = list(BatchStager(host_batches(), DEV, target_generator=gen))
     torch.cuda.synchronize()
     gen.check()
+    guard.check()                                 # the stager's device buffers and the three ring slots
     assert len(staged) == len(plain) == 3
     for b, p, want in zip(staged, plain, refs):
         assert sorted(p) == ['depth', 'instance', 'name', 'orientations', 'rgb', 'scene', 'semantic']
         assert sorted(b) == sorted(list(p) + ['targets'])
         assert_targets(b['targets'], want)
         assert torch.equal(b['rgb'], p['rgb']) and torch.equal(b['semantic'], p['semantic'])
+
+
+# every test above once more as `<name>_poison00`, on 0x00 payloads (True, 255 and -1 are legal values)
+guard.second_payload(globals())
