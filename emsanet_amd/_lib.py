@@ -101,6 +101,7 @@ SIGNATURES = {
     'emsa_to_nhwc_t': (c_int, [c_int32, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int64, c_int64,
                                c_int64, c_int64, _P]),
     'emsa_conv1d_wino_set_spec': (c_int, [c_int32]),
+    'emsa_wino_set_u_tiled': (c_int, [c_int32]),
     'emsa_conv1d_wino_spec_launches': (c_int, []),
     'emsa_conv1d_wino_resmask_supported': (c_int, [_GP, c_int32]),
     'emsa_conv1d_wino_resmask': (c_int, [_GP, _P, _P, _P, _P, c_int32, _P, _P]),

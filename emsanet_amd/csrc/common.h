@@ -63,6 +63,20 @@ __device__ __forceinline__ void emsa_wino2d_u(const float g[9], float u[16]) {
   }
 }
 
+// U of the row-Winograd convs (conv_wino.hip).  1-D convs whose channel counts fill whole tiles keep
+// it per 64-channel tile and 16-channel K step, [n/64][K/16][4 comps][64][16]: the 16 KiB a workgroup
+// stages per K step are one contiguous block.  Everything else ([4][n][R*K]): the three-row form, a
+// channel tail, an n that is no multiple of 64.  Writers and readers ask this one rule, each for its
+// own (n, K): forward n = cout, K = cin; data gradient n = cin, K = cout.
+__host__ __device__ __forceinline__ bool wino_u_tiled(int R, int n_ch, int k_ch) {
+  return R == 1 && n_ch % 64 == 0 && k_ch % 16 == 0;
+}
+// element (comp, n, k) of a U with K = R * k_ch columns; `tiled` = the rule above (and the switch)
+__host__ __device__ __forceinline__ size_t wino_u_at(bool tiled, int comp, int n, int k, int n_ch, int K) {
+  return tiled ? ((((size_t)(n >> 6) * (K >> 4) + (k >> 4)) * 4 + comp) << 10) + ((n & 63) << 4) + (k & 15)
+               : ((size_t)comp * n_ch + n) * K + k;
+}
+
 // ---- 16-bit activation storage (BASELINE configs 3 / 5: bf16 training, fp16|bf16 inference) ------
 // Kernels templated on the STORAGE type T of their activation tensors read / write through these
 // overloads; all arithmetic stays fp32 in registers.  Four consecutive channels = one 8-byte access

@@ -13,8 +13,16 @@
 // different lines) x 64 output channels, 4 waves: wave j owns Winograd component j (2 MFMA
 // tiles of 32x32).  Per K step (16 channels) the RAW input rows d0..d3 of every pair are staged
 // once ([4][32][20] floats) and wave j forms its V_j operand on the fly as the sum/difference of
-// two conflict-free ds_read_b128; U_j is staged as [4][64][20].  Single LDS buffer + register
-// prefetch (30 KiB -> 5 workgroups per CU).  The epilogue transposes m_j through LDS, applies the
+// two conflict-free ds_read_b128; U_j is staged as [4][64][16] (chunks swizzled by the row).  Single
+// LDS buffer + register prefetch (24 KiB -> 5 workgroups per CU).
+// U in memory (wino_u_tiled / wino_u_at in common.h, asked by every packer and by the launcher): for
+// the 1-D convs with n % 64 == 0 and K % 16 == 0 it is [n/64][K/16][4][64][16] -- the 16 KiB a
+// workgroup stages per K step are ONE contiguous block in the order of the LDS image, a wave load
+// reads 1 KiB and the K advance is the scalar offset s * 16384.  Stored [4][n][K] (still the layout of
+// the three-row form, of a channel tail and of an n that is no multiple of 64) a wave load fetched
+// 16 pieces of 64 B from 16 rows, and on gfx950 half a 128-B line costs an L2 request of its own:
+// 71 against 126 GB/s per CU of useful bytes (tools/l2_read_peak.hip pieces).
+// The epilogue transposes m_j through LDS, applies the
 // output transform and the same fused epilogue as conv_igemm (bias, BatchNorm statistics
 // partials, folded BatchNorm, residual, ReLU, ReLU-backward mask) with 16-B stores.
 #include <atomic>
@@ -86,6 +94,7 @@ struct WinoArgs {
   int L, PL, A, MP;                 // line length, pairs per line, lines per image, total pairs
   int k_ch, n_ch;                   // k_ch = R * c_in (GEMM K), n_ch output channels
   int R, c_in, ksteps_c;            // perpendicular taps (1: 1-D conv, 3: 3x3), channels and K steps per tap
+  int u_tiled;                      // u is [n/64][K step][4][64][16] (wino_u_tiled), else [4][n][k_ch]
   int in_simg, in_sa, in_sb;        // input element strides (image, line, position on the line)
   int px_simg, px_sa, px_sb;        // output PIXEL strides (x ld_out / ld_res / ld_mask)
   int tiles_m, tiles_n, ksteps;
@@ -216,11 +225,22 @@ __global__ __launch_bounds__(256, kWN == 64 ? (BNB ? 4 : 5) : 6) void conv1d_win
   } else {
     setup_a(mt);
   }
+  // U: tiled (wino_u_tiled, common.h), the tile's K step is one contiguous 16 KiB block in
+  // exactly the order of the LDS image -- a wave load reads 1 KiB, the K advance is 16 KiB; a 32-wide
+  // tile takes its half of each component's 64 rows.  Otherwise rows of [4][n][k_ch], 64 B per K step.
+  // Both are  tile base + comp * component stride + (row * row length + c4) * 4  with wave-uniform
+  // terms, so the layout costs the prologue no vector instruction and the K loop none either.
+  const bool u_tiled = p.u_tiled != 0;
+  const uint32_t u_step = u_tiled ? 16384u : (uint32_t)kWK * 4u;              // K advance, bytes
+  const uint32_t u_row = u_tiled ? 16u : (uint32_t)p.k_ch;                    // row length, floats
+  const uint32_t u_comp = u_tiled ? 4096u : (uint32_t)(p.n_ch * p.k_ch) * 4u;
+  const uint32_t u_base = u_tiled ? (uint32_t)((n0 >> 6) * p.ksteps) * 16384u + (uint32_t)(n0 & 63) * 64u
+                                  : (uint32_t)(n0 * p.k_ch) * 4u;
 #pragma unroll
   for (int j = 0; j < BLD; ++j) {
     const int rowid = (tid >> 2) + 64 * j;          // 0..4*kWN-1 = comp*kWN + n
-    const int comp = rowid / kWN, n = n0 + (rowid % kWN);
-    b_voff[j] = n < p.n_ch ? (uint32_t)((comp * p.n_ch + n) * p.k_ch + c4) * 4u : kOOBw;
+    const int comp = rowid / kWN, nl = rowid % kWN;
+    b_voff[j] = n0 + nl < p.n_ch ? u_base + comp * u_comp + ((uint32_t)nl * u_row + c4) * 4u : kOOBw;
   }
   // offsets of the tile's pixels on kernel row r (r = 0 only for the 1-D convs): the line shifts
   // by r - 1 and may leave the image (zero padding)
@@ -243,14 +263,16 @@ __global__ __launch_bounds__(256, kWN == 64 ? (BNB ? 4 : 5) : 6) void conv1d_win
 #pragma unroll
       for (int j = 0; j < 2; ++j) ra[j] = wbuf_ld4s(rs_in, a_voff[j], so);
 #pragma unroll
-      for (int j = 0; j < BLD; ++j) rb[j] = wbuf_ld4s(rs_u, b_voff[j], so);
+      for (int j = 0; j < BLD; ++j) rb[j] = wbuf_ld4s(rs_u, b_voff[j], (uint32_t)s * u_step);
       return;
     }
     // K step s = (perpendicular tap r, channel chunk), all wave-uniform
     const int r = s >= 2 * p.ksteps_c ? 2 : (s >= p.ksteps_c ? 1 : 0);
     const int ch = (s - r * p.ksteps_c) * kWK;                     // first input channel
     if (ch == 0) set_row(r);
-    const uint32_t sa = (uint32_t)ch * 4u, sb = (uint32_t)(r * p.c_in + ch) * 4u;
+    // (U: u_step = 64 B along a row, or one tiled block -- R = 1 there, so r = 0)
+    const uint32_t sa = (uint32_t)ch * 4u;
+    const uint32_t sb = (uint32_t)(r * p.c_in) * 4u + (uint32_t)(s - r * p.ksteps_c) * u_step;
     // last, partial channel chunk (c_in not a multiple of 16): the lanes beyond c_in go out of
     // range.  One v_and_or per load with a wave-uniform mask -- NOT a branch around the loads: a
     // control-flow join behind them makes the compiler wait for the data right there, before the
@@ -698,37 +720,39 @@ __global__ __launch_bounds__(256, kWN == 64 ? (BNB ? 4 : 5) : 6) void conv1d_win
 // Winograd along kw): forward (n = cout, K = cin) and/or data gradient (n = cin, K = cout, taps
 // flipped in both directions)
 __global__ void pack_wino_kernel(const float* __restrict__ w, float* __restrict__ u,
-                                 float* __restrict__ ud, int cout, int cin, int R) {
+                                 float* __restrict__ ud, int cout, int cin, int R, int utile) {
   const int total = cout * cin * R;
+  const bool tu = utile && wino_u_tiled(R, cout, cin), td = utile && wino_u_tiled(R, cin, cout);
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
     const int r = i % R, ci = (i / R) % cin, co = i / (R * cin);
     const float* g = w + (size_t)i * 3;          // [co][ci][r][3]
     const float g0 = g[0], g1 = g[1], g2 = g[2];
     const float s = 0.5f * (g0 + g2), h = 0.5f * g1;
     if (u) {
-      const size_t NK = (size_t)cout * R * cin, o = ((size_t)co * R + r) * cin + ci;
-      u[0 * NK + o] = g0;
-      u[1 * NK + o] = s + h;
-      u[2 * NK + o] = s - h;
-      u[3 * NK + o] = g2;
+      const int k = r * cin + ci, K = R * cin;
+      u[wino_u_at(tu, 0, co, k, cout, K)] = g0;
+      u[wino_u_at(tu, 1, co, k, cout, K)] = s + h;
+      u[wino_u_at(tu, 2, co, k, cout, K)] = s - h;
+      u[wino_u_at(tu, 3, co, k, cout, K)] = g2;
     }
     if (ud) {
-      const size_t NK = (size_t)cin * R * cout, o = ((size_t)ci * R + (R - 1 - r)) * cout + co;
-      ud[0 * NK + o] = g2;
-      ud[1 * NK + o] = s + h;
-      ud[2 * NK + o] = s - h;
-      ud[3 * NK + o] = g0;
+      const int k = (R - 1 - r) * cout + co, K = R * cout;
+      ud[wino_u_at(td, 0, ci, k, cin, K)] = g2;
+      ud[wino_u_at(td, 1, ci, k, cin, K)] = s + h;
+      ud[wino_u_at(td, 2, ci, k, cin, K)] = s - h;
+      ud[wino_u_at(td, 3, ci, k, cin, K)] = g0;
     }
   }
 }
 
 // same transform from the PACKED implicit-GEMM layout wp[tap = r*3 + t][n][k] (what the merged /
-// channel-padded head convs are assembled in): U_j[n][r*k_ch + k]; flip = 1 for the data-gradient
+// channel-padded head convs are assembled in): U_j[n][r*k_ch + k] placed by wino_u_at; flip = 1 for the data-gradient
 // pack ([tap][cin][cout], taps not flipped there) -> taps flipped here
 __global__ void pack_wino_packed_kernel(const float* __restrict__ wp, float* __restrict__ u, int n,
-                                        int k, int R, int flip) {
+                                        int k, int R, int flip, int utile) {
   const int total = n * k * R;
-  const size_t NK = (size_t)total, plane = (size_t)n * k;
+  const size_t plane = (size_t)n * k;
+  const bool tu = utile && wino_u_tiled(R, n, k);
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
     const int kk = i % k, r = (i / k) % R, nn = i / (k * R);
     const int rs = flip ? R - 1 - r : r;
@@ -736,11 +760,10 @@ __global__ void pack_wino_packed_kernel(const float* __restrict__ wp, float* __r
     float g0 = g[0], g1 = g[plane], g2 = g[2 * plane];
     if (flip) { const float t = g0; g0 = g2; g2 = t; }
     const float s = 0.5f * (g0 + g2), h = 0.5f * g1;
-    const size_t o = ((size_t)nn * R + r) * k + kk;
-    u[0 * NK + o] = g0;
-    u[1 * NK + o] = s + h;
-    u[2 * NK + o] = s - h;
-    u[3 * NK + o] = g2;
+    u[wino_u_at(tu, 0, nn, r * k + kk, n, R * k)] = g0;
+    u[wino_u_at(tu, 1, nn, r * k + kk, n, R * k)] = s + h;
+    u[wino_u_at(tu, 2, nn, r * k + kk, n, R * k)] = s - h;
+    u[wino_u_at(tu, 3, nn, r * k + kk, n, R * k)] = g2;
   }
 }
 
@@ -771,7 +794,7 @@ __device__ __forceinline__ void pack_store(float* base, int r, int n, int k, int
     base[idx] = v;
 }
 __global__ __launch_bounds__(256) void pack_batch_kernel(const EmsaPackJob* __restrict__ jobs,
-                                                         int n_jobs) {
+                                                         int n_jobs, int utile) {
   // 32 (co) x 32 (ci) tiles: reads and forward-layout writes run along ci, the transposed
   // (data-gradient) layouts are written along co through an LDS transpose -- the element-wise
   // version scattered 4-byte stores with stride cout and took 1.2 ms for the 63 M weights
@@ -856,9 +879,10 @@ __global__ __launch_bounds__(256) void pack_batch_kernel(const EmsaPackJob* __re
         const float sm = 0.5f * (g0 + g2), h = 0.5f * g1;
         vals[k][0] = g0; vals[k][1] = sm + h; vals[k][2] = sm - h; vals[k][3] = g2;
         if (ok && jb.dst0) {
-          const size_t NK = (size_t)coT * R * ciT, o = ((size_t)(co + coO) * R + r) * ciT + ci + ciO;
+          const bool tu = utile && wino_u_tiled(R, coT, ciT);
 #pragma unroll
-          for (int j = 0; j < 4; ++j) jb.dst0[j * NK + o] = vals[k][j];
+          for (int j = 0; j < 4; ++j)
+            jb.dst0[wino_u_at(tu, j, co + coO, r * ciT + ci + ciO, coT, R * ciT)] = vals[k][j];
         }
       } else {
         const float v = ok ? jb.src[((size_t)co * cin + ci) * taps + r] : 0.f;
@@ -880,12 +904,12 @@ __global__ __launch_bounds__(256) void pack_batch_kernel(const EmsaPackJob* __re
         if (ci < cin && co < cout) {
           if (wino) {
             // data gradient: taps flipped (components 0 <-> 3) and kernel rows reversed
-            const size_t NK = (size_t)ciT * R * coT,
-                         o = ((size_t)(ci + ciO) * R + (R - 1 - r)) * coT + co + coO;
-            jb.dst1[0 * NK + o] = tr[3][tx][ty + 8 * k];
-            jb.dst1[1 * NK + o] = tr[1][tx][ty + 8 * k];
-            jb.dst1[2 * NK + o] = tr[2][tx][ty + 8 * k];
-            jb.dst1[3 * NK + o] = tr[0][tx][ty + 8 * k];
+            const bool td = utile && wino_u_tiled(R, ciT, coT);
+            const int n = ci + ciO, kk = (R - 1 - r) * coT + co + coO, K = R * coT;
+            jb.dst1[wino_u_at(td, 0, n, kk, ciT, K)] = tr[3][tx][ty + 8 * k];
+            jb.dst1[wino_u_at(td, 1, n, kk, ciT, K)] = tr[1][tx][ty + 8 * k];
+            jb.dst1[wino_u_at(td, 2, n, kk, ciT, K)] = tr[2][tx][ty + 8 * k];
+            jb.dst1[wino_u_at(td, 3, n, kk, ciT, K)] = tr[0][tx][ty + 8 * k];
           } else {
             pack_store(jb.dst1, r, ci + ciO, co + coO, ciT, coT, tr[0][tx][ty + 8 * k], jb.kind);
           }
@@ -902,7 +926,21 @@ inline void magic(uint32_t d, uint32_t& mul, uint32_t& sh) {
   mul = (uint32_t)(((1ull << 32) * ((1ull << s) - d)) / d + 1);
 }
 
+// EMSA_WINO_UTILE=0 (read once) or emsa_wino_set_u_tiled(0): packers and launchers alike keep
+// [4][n][K] for every shape and every launch takes the generic kernel (the reference of
+// tests/test_wino_u_tiled_gpu.py and the A/B switch of tools/conv_bench.py; not for the model: a U
+// packed under one setting must be read under the same)
+std::atomic<int> g_wino_utile{[] {
+  const char* e = getenv("EMSA_WINO_UTILE");
+  return e && e[0] == '0' ? 0 : 1;
+}()};
+inline int wino_utile_on() { return g_wino_utile.load(std::memory_order_relaxed); }
+
 }  // namespace
+
+extern "C" int emsa_wino_set_u_tiled(int32_t on) {
+  return g_wino_utile.exchange(on ? 1 : 0, std::memory_order_relaxed);
+}
 
 extern "C" int emsa_pack_wino(const float* w_oihw, float* u, float* u_dgrad, int32_t cout,
                               int32_t cin, int32_t rows, void* stream) {
@@ -912,7 +950,7 @@ extern "C" int emsa_pack_wino(const float* w_oihw, float* u, float* u_dgrad, int
   int grid = (total + 255) / 256;
   if (grid > 2048) grid = 2048;
   hipLaunchKernelGGL(pack_wino_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w_oihw, u,
-                     u_dgrad, cout, cin, rows);
+                     u_dgrad, cout, cin, rows, wino_utile_on());
   return emsa_launch_status();
 }
 
@@ -921,7 +959,7 @@ extern "C" int emsa_pack_batch(const EmsaPackJob* jobs_device, int32_t n_jobs,
   if (!jobs_device) return EMSA_E_ARG;
   if (n_jobs < 1 || total_blocks < n_jobs) return EMSA_E_SHAPE;
   hipLaunchKernelGGL(pack_batch_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream,
-                     jobs_device, n_jobs);
+                     jobs_device, n_jobs, wino_utile_on());
   return emsa_launch_status();
 }
 
@@ -933,7 +971,7 @@ extern "C" int emsa_pack_wino_packed(const float* w_packed, float* u, int32_t n_
   int grid = (total + 255) / 256;
   if (grid > 2048) grid = 2048;
   hipLaunchKernelGGL(pack_wino_packed_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream,
-                     w_packed, u, n_ch, k_ch, rows, flip ? 1 : 0);
+                     w_packed, u, n_ch, k_ch, rows, flip ? 1 : 0, wino_utile_on());
   return emsa_launch_status();
 }
 
@@ -1046,6 +1084,7 @@ static int conv1d_wino_impl(const EmsaConvGeom* g, const float* in, const float*
   a.R = g->kh == 3 && g->kw == 3 ? 3 : 1;
   a.c_in = g->k_ch;
   a.k_ch = a.R * g->k_ch; a.n_ch = g->n_ch;
+  a.u_tiled = wino_utile_on() && wino_u_tiled(a.R, g->n_ch, g->k_ch) ? 1 : 0;
   a.in_simg = (int)g->in_img_stride;
   a.in_sa = aw ? (int)g->in_row_stride : g->in_px_stride;
   a.in_sb = aw ? g->in_px_stride : (int)g->in_row_stride;

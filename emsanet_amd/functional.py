@@ -346,8 +346,9 @@ def wino_rows(spec):
 
 
 def pack_wino(w, fwd=True, dgrad=False):
-    """OIHW [cout][cin][3x1|1x3] -> Winograd F(2,3) weights U [4][n][k]: forward (n,k = cout,cin)
-    and/or data gradient (n,k = cin,cout, flipped taps), one launch.  -> (u or None, ud or None)"""
+    """OIHW [cout][cin][3x1|1x3] -> Winograd F(2,3) weights U, 4 * n * k floats in the layout the
+    conv reads for its (n, k) (include/emsanet_hip.h): forward (n,k = cout,cin) and/or data gradient
+    (n,k = cin,cout, flipped taps), one launch.  -> (u or None, ud or None)"""
     cout, cin, kh, kw = w.shape
     rows = 3 if (kh, kw) == (3, 3) else 1
     buf = _empty((int(fwd) + int(dgrad), 4 * rows * cout * cin), w.device)

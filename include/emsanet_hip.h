@@ -129,10 +129,13 @@ int emsa_conv_wgrad(const EmsaConvGeom* g, const float* in, const float* dout, f
  * GEMMs over half the pixels instead of 3 over all (1.5x fewer matrix instructions, fp32-exact
  * coefficients 1 and 1/2); a 3x3 conv is transformed along W and its three kernel rows are part of
  * the GEMM K dimension (K = 3 * k_ch).
- * Same arguments and fused epilogue as emsa_conv_igemm, but `u` = transformed weights
- * [4][n_ch][rows * k_ch] (rows = 1 or 3 kernel rows) from emsa_pack_wino (from the OIHW parameter;
+ * Same arguments and fused epilogue as emsa_conv_igemm, but `u` = transformed weights, 4 * n_ch *
+ * rows * k_ch floats (rows = 1 or 3 kernel rows) from emsa_pack_wino (from the OIHW parameter;
  * u_dgrad: data-gradient weights, taps flipped, channels transposed) or emsa_pack_wino_packed
- * (from the packed [tap][n][k] layout, flip = 1 for a data-gradient pack);
+ * (from the packed [tap][n][k] layout, flip = 1 for a data-gradient pack).  Layout: with rows = 1,
+ * n_ch % 64 == 0 and k_ch % 16 == 0, [n_ch/64][k_ch/16][4 comps][64][16] -- what a workgroup
+ * stages for one K step is one contiguous 16 KiB block --, otherwise [4][n_ch][rows * k_ch].  The
+ * packers and the conv apply the same rule, each to its own (n_ch, k_ch): `u` is opaque to callers.
  * stats partial rows = emsa_conv1d_wino_stats_rows(g).                                          */
 int emsa_conv1d_wino_supported(const EmsaConvGeom* g);
 int emsa_conv1d_wino_stats_rows(const EmsaConvGeom* g);
@@ -174,6 +177,11 @@ int emsa_conv1d_wino_bnb(const EmsaConvGeom* g, const float* dy, const float* u,
  * instantiation so far (tests read it to see which kernel the dispatch chose).                   */
 int emsa_conv1d_wino_set_spec(int32_t on);
 int emsa_conv1d_wino_spec_launches(void);
+/* on = 0: the packers write and emsa_conv1d_wino* read [4][n_ch][rows * k_ch] for EVERY shape (the
+ * layout before the tiled one; tests and tools/conv_bench.py compare the two), on = 1 restores the
+ * rule above.  Returns the previous setting; EMSA_WINO_UTILE=0 starts the process with 0.  A `u`
+ * must be read under the setting it was packed under.                                            */
+int emsa_wino_set_u_tiled(int32_t on);
 int emsa_conv1d_wino_resmask_supported(const EmsaConvGeom* g, int32_t ld_res);
 int emsa_conv1d_wino_resmask(const EmsaConvGeom* g, const float* dy, const float* u, float* out,
                              const float* residual, int32_t ld_res, const uint64_t* res_bits,
@@ -192,8 +200,9 @@ int emsa_conv1d_wino_inbn(const EmsaConvGeom* g, const float* in, const float* u
 int emsa_conv_wgrad_inbn(const EmsaConvGeom* g, const float* in, const float* dout, float* dw,
                          float* dbias, float* ws, const float* in_scale, const float* in_shift,
                          void* stream);
-/* u (forward weights [4][cout][rows*cin]) and/or u_dgrad (data-gradient weights
- * [4][cin][rows*cout]) from the OIHW taps in one launch; either output may be NULL              */
+/* u (forward weights, n = cout, k = cin) and/or u_dgrad (data-gradient weights, n = cin, k = cout)
+ * from the OIHW taps in one launch, each in the layout emsa_conv1d_wino reads for its (n, k);
+ * either output may be NULL                                                                      */
 int emsa_pack_wino(const float* w_oihw, float* u, float* u_dgrad, int32_t cout, int32_t cin,
                    int32_t rows, void* stream);
 int emsa_pack_wino_packed(const float* w_packed, float* u, int32_t n_ch, int32_t k_ch,
