@@ -2533,41 +2533,113 @@ bool dout_is_aligned(const EmsaConvGeom* g, const float* dout) {
   return ((g->ld_out & 3) == 0) && ((g->n_ch & 3) == 0) && ((((uintptr_t)dout) & 15) == 0);
 }
 
-}  // namespace
-
-// bytes of workspace for the deterministic two-pass weight gradient of `g` (0: not available for
-// this geometry -> emsa_conv_wgrad accumulates with atomics into the packed layout)
-namespace {
+// ---- weight gradient: which kernel runs, with what grid, LDS, workspace and reduction ---------
+// (the switches below are read once: `static const bool v = env_is(...)`)
+bool env_is(const char* name, char c) {
+  const char* e = getenv(name);
+  return e && e[0] == c;
+}
 // the 16-bit activations' weight gradient: direct bf16 kernel (default) or, EMSA_WGRAD16=wino, the
-// Winograd F(3,2) kernel with bf16 loads (A/B)
-bool wgrad16_direct() {
-  static const bool v = [] {
-    const char* e = getenv("EMSA_WGRAD16");
-    return !(e && e[0] == 'w');
-  }();
-  return v;
+// Winograd F(3,2) kernel with bf16 loads (A/B).  The geometry admits the direct kernel with 8-byte
+// accesses: 4 channels (dout_is_aligned checks dy)
+bool direct16_geom(const EmsaConvGeom* g) {
+  static const bool direct = !env_is("EMSA_WGRAD16", 'w');
+  return direct && !(g->k_ch & 3);
 }
 // EMSA_WGRAD16_TR=0: the stride-1 3-tap weight gradients on conv_wgrad1d_h_kernel (register
-// transposes) instead of conv_wgrad1d_tr_kernel (ds_read_b64_tr_b16)
-bool wgrad16_tr() {
-  static const bool v = [] {
-    const char* e = getenv("EMSA_WGRAD16_TR");
-    return !(e && e[0] == '0');
-  }();
-  return v;
+// transposes) instead of conv_wgrad1d_tr_kernel (ds_read_b64_tr_b16).  That kernel moves 16-byte
+// chunks: every pixel row of both tensors starts on a 16-byte boundary (NULL pointers: assumed
+// aligned, as the workspace queries ask)
+bool wgrad16_tr_ok(const EmsaConvGeom* g, const void* in, const void* dout) {
+  static const bool tr = !env_is("EMSA_WGRAD16_TR", '0');
+  return tr && !((g->k_ch | g->n_ch | g->ld_out | g->in_px_stride | g->in_row_stride | g->in_img_stride) & 7) &&
+         !((((uintptr_t)in) | ((uintptr_t)dout)) & 15);
 }
-// geometry admits the direct 16-bit kernel (8-byte accesses: 4 channels; dout_is_aligned checks dy)
-bool direct16_geom(const EmsaConvGeom* g) { return wgrad16_direct() && !(g->k_ch & 3); }
-// wino16: the storage type has the opt-in Winograd form (bf16; see conv_wgrad_impl)
-int64_t wgrad_ws_bytes(const EmsaConvGeom* g, size_t esize, bool wino16 = true) {
-  if (!geom_ok(g)) return 0;
-  Wgrad1dPlan pl;
+
+// workspace of one two-pass job, in floats: the split-K partial tiles [ksplit][R][n_tiles][taps][64][64],
+// the bias rows [ksplit][n_co_tiles][64] behind them
+struct WgradWsLayout { int64_t job_floats, bias_off; };
+WgradWsLayout wgrad_ws_layout(const Wgrad1dPlan& pl) {
+  const int64_t tiles = (int64_t)pl.ksplit * pl.w.n_tiles * pl.w.R * pl.w.taps * 4096;
+  return {tiles + (int64_t)pl.ksplit * pl.w.n_co_tiles * 64, tiles};
+}
+
+// second pass: none (atomics), one thread per (tile, co) row summing all splits -- many tiles, few
+// splits, see wgrad1d_reduce_rows_body -- or the plain form (EMSA_WGRAD_REDUCE_ROWS=0: always plain, A/B)
+enum WgradReduce { WR_NONE = 0, WR_ROWS, WR_PLAIN };
+WgradReduce wgrad_reduce_kind(bool has_ws, int ksplit, int n_tiles) {
+  static const bool rows_on = !env_is("EMSA_WGRAD_REDUCE_ROWS", '0');
+  return !has_ws ? WR_NONE : rows_on && ksplit <= 16 && n_tiles >= 32 ? WR_ROWS : WR_PLAIN;
+}
+int wgrad_reduce_grid(WgradReduce kind, const Wgrad1dArgs& w) {
+  return (kind == WR_ROWS ? w.n_tiles * 4 : w.n_tiles * w.R * w.taps * 64) + w.n_co_tiles;
+}
+
+enum WgradKernel {
+  WG_REFUSED = 0, WG_TAPS7, WG_TAPS2, WG_TAPS1, WG_TAPS3,   // conv_wgrad_kernel: tap groups, atomics
+  WG_1D, WG_WINO, WG_WINO_XBN, WG_WINO_BF16,     // conv_wgrad1d_kernel / conv_wgrad1d_wino_kernel
+  WG_H0, WG_H1, WG_H2, WG_TR, WG_TR_XBN          // conv_wgrad1d_h_kernel<T, MODE> / conv_wgrad1d_tr_kernel<T, XBN>
+};
+// what a launch of one geometry is decided by; the tap-group kernels size their own grid and LDS
+// in launch_wgrad (grid = lds = 0 here)
+struct WgradChoice {
+  WgradKernel kernel;
+  int err;                 // WG_REFUSED: the code the entry point returns
+  Wgrad1dPlan pl;          // WG_1D and later
+  int grid, cls;
+  size_t lds;
+  WgradReduce reduce;
+};
+// THE selection rule.  esize / f16: the storage type; fold: the x operand is relu(in * scale + shift)
+// formed in the loader; has_ws: two-pass form; in / dout: NULL = assume aligned (workspace queries).
+WgradChoice choose_wgrad(const EmsaConvGeom* g, size_t esize, bool f16, bool fold, bool has_ws,
+                         const void* in, const void* dout) {
+  WgradChoice c{};
+  auto refuse = [&c](int err) { c.kernel = WG_REFUSED; c.err = err; return c; };
+  auto pick = [&c](WgradKernel k, size_t lds) { c.kernel = k; c.lds = lds; };
+  if (fold && f16) return refuse(EMSA_E_ARG);       // the loader fold is a bf16 / fp32 form
   const bool half = esize != sizeof(float);
-  const bool d16 = half && direct16_geom(g);
-  if (!plan_wgrad1d(g, dout_is_aligned(g, nullptr), pl, esize, d16)) return 0;
-  if (half && !d16 && !(pl.wino && wino16)) return 0;
-  return (int64_t)pl.ksplit * ((int64_t)pl.w.n_tiles * pl.w.R * pl.w.taps * 4096 +
-                               (int64_t)pl.w.n_co_tiles * 64) * (int64_t)sizeof(float);
+  const bool aligned = dout_is_aligned(g, (const float*)dout);
+  // 16-bit kernels: 8-byte accesses to both tensors (dout_is_aligned: 16 for dy)
+  if (half && (!aligned || (((uintptr_t)in) & 7))) return refuse(EMSA_E_SHAPE);
+  const bool direct16 = half && direct16_geom(g);
+  Wgrad1dPlan& pl = c.pl;
+  // EMSA_WGRAD16=wino rounds the Winograd-transformed operands to bf16: a bf16 form only.  fp16
+  // storage under that switch runs the tap-group kernel (fp32 MFMA on the converted values).
+  const bool one_d = plan_wgrad1d(g, aligned, pl, esize, direct16) &&
+                     (!half || direct16 || (pl.wino && !f16));
+  if (!one_d) {
+    // no workspace (its query answered 0), and only the 1-D forms fold the input's BatchNorm
+    if (has_ws || fold) return refuse(EMSA_E_SHAPE);
+    const int taps = g->kh * g->kw;
+    // (taps == 2: the one-channel stem.  A 128x128 tile was measured slower for the 1x1 convs:
+    //  96 / 82 us vs 66 / 63 us at 128 / 256 channels -- four times the split-K partial-tile volume
+    //  per workgroup)
+    c.kernel = taps == 7 && g->k_ch <= 32 ? WG_TAPS7 : taps == 2 && g->k_ch <= 32 ? WG_TAPS2 :
+               taps == 1 ? WG_TAPS1 : WG_TAPS3;
+    return c;
+  }
+  const Wgrad1dArgs& w = pl.w;
+  c.grid = w.n_tiles * w.R * pl.ksplit;
+  c.cls = half ? kProfClassWgradH : (w.R == 3 ? kProfClassWgrad3x3 : 7);
+  c.reduce = wgrad_reduce_kind(has_ws, pl.ksplit, w.n_tiles);
+  static const bool bf16 = env_is("EMSA_BF16_MFMA", '1');
+  const size_t wino_lds = (size_t)(16 * 4 * (64 + 64)) * sizeof(float), h_rows = (size_t)64 * kWH_ROW * esize;
+  const size_t fold_lds = fold ? 2 * 64 * sizeof(float) : 0;       // the {scale, shift} table
+  if (!half && !pl.wino) pick(WG_1D, (size_t)(32 * 64 + 34 * 64) * sizeof(float));
+  // the fold is tested BEFORE the opt-in bf16-MFMA form: that kernel has no loader fold and would
+  // multiply against the raw BatchNorm input -- ADVICE r3; the fold stays exact fp32
+  else if (!half) pick(fold ? WG_WINO_XBN : bf16 ? WG_WINO_BF16 : WG_WINO, wino_lds + fold_lds);
+  // EMSA_WGRAD16=wino: E / D are formed in fp32 and rounded to bf16 as they enter LDS, one
+  // v_mfma_f32_32x32x16_bf16 per Winograd component and K step
+  else if (!direct16) pick(WG_WINO_BF16, wino_lds);
+  else if (pl.mode != 0) pick(pl.mode == 1 ? WG_H1 : WG_H2, (pl.mode == 1 ? 2 : 3) * h_rows);
+  else if (wgrad16_tr_ok(g, in, dout)) pick(fold ? WG_TR_XBN : WG_TR, (size_t)2 * kWT_IMG * esize + fold_lds);
+  else pick(WG_H0, 2 * h_rows);
+  // the loader fold exists in the fp32 Winograd form and the transposed-read kernel only (not in
+  // the direct forms, conv_wgrad1d_kernel / conv_wgrad1d_h_kernel), one kernel row
+  if (fold && !((c.kernel == WG_WINO_XBN || c.kernel == WG_TR_XBN) && w.R == 1)) return refuse(EMSA_E_SHAPE);
+  return c;
 }
 }  // namespace
 #if EMSA_WH_DBG
@@ -2575,156 +2647,112 @@ extern "C" int emsa_wgrad1d_h_dbg_read(long long* host, int n_entries) {
   return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_wh_dbg), (size_t)n_entries * 8) == hipSuccess ? 0 : -3;
 }
 #endif
-extern "C" int64_t emsa_conv_wgrad_ws_bytes(const EmsaConvGeom* g) {
-  return wgrad_ws_bytes(g, sizeof(float));
-}
-// workspace of emsa_conv_wgrad_t for activations of `dtype` (the split-K plan depends on it)
-extern "C" int64_t emsa_conv_wgrad_ws_bytes_t(int32_t dtype, const EmsaConvGeom* g) {
-  return wgrad_ws_bytes(g, dtype == EMSA_DT_F32 ? sizeof(float) : 2, dtype != EMSA_DT_F16);
+namespace {
+// the reduction pass of a two-pass launch (plain and rows form take the same arguments)
+void launch_wgrad_reduce(WgradReduce kind, const Wgrad1dPlan& pl, hipStream_t st) {
+  if (kind == WR_NONE) return;
+  const Wgrad1dArgs& w = pl.w;
+  hipLaunchKernelGGL(kind == WR_ROWS ? wgrad1d_reduce_rows_kernel : wgrad1d_reduce_kernel,
+                     dim3(wgrad_reduce_grid(kind, w)), dim3(256), 0, st, w.ws, w.ws_bias, pl.ksplit,
+                     w.n_tiles, w.n_ci_tiles, w.n_co_tiles, w.n_ch, w.k_ch, w.R, w.dw, w.dbias, w.taps);
 }
 
-namespace {
+// launches what choose_wgrad chose (never WG_REFUSED; it answers no kernel T has no instantiation of)
 template <typename T>
-int conv_wgrad_impl(const EmsaConvGeom* g, const T* in_t, const T* dout_t, float* dw, float* dbias,
-                    float* ws, void* stream, const float* in_scale = nullptr,
-                    const float* in_shift = nullptr) {
-  constexpr bool kHalf = sizeof(T) != 4;
-  // EMSA_WGRAD16=wino rounds the Winograd-transformed operands to bf16: a bf16 form only.  fp16
-  // storage under that switch runs the tap-group kernel (fp32 MFMA on the converted values).
-  constexpr bool kF16 = std::is_same<T, emsa_f16>::value;
+int launch_wgrad_choice(const WgradChoice& c, const WgradArgs& a, double wbytes, hipStream_t st) {
+  constexpr bool kHalf = sizeof(T) != 4, kF16 = std::is_same<T, emsa_f16>::value;
+  const Wgrad1dArgs& w = c.pl.w;
+  auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(c.grid), dim3(256), c.lds, st, w); };
+  const int ps = c.kernel >= WG_1D ? prof_begin(c.cls, algo_flops(a.g), st, wbytes) : -1;
+  switch (c.kernel) {
+    case WG_TAPS7: return launch_wgrad<64, 32, 7, 2, 1, 2, T>(a, st);
+    case WG_TAPS2: return launch_wgrad<64, 32, 2, 2, 1, 2, T>(a, st);
+    case WG_TAPS1: return launch_wgrad<64, 64, 1, 2, 2, 1, T>(a, st);
+    case WG_TAPS3: return launch_wgrad<64, 64, 3, 2, 2, 1, T>(a, st);
+    case WG_1D: if constexpr (!kHalf) go(conv_wgrad1d_kernel<64, 64>); break;
+    case WG_WINO: if constexpr (!kHalf) go(conv_wgrad1d_wino_kernel<64, 64>); break;
+    case WG_WINO_XBN: if constexpr (!kHalf) go(conv_wgrad1d_wino_kernel<64, 64, false, float, true>); break;
+    case WG_WINO_BF16: if constexpr (!kF16) go(conv_wgrad1d_wino_kernel<64, 64, true, T>); break;
+    case WG_H0: if constexpr (kHalf) go(conv_wgrad1d_h_kernel<T, 0>); break;
+    case WG_H1: if constexpr (kHalf) go(conv_wgrad1d_h_kernel<T, 1>); break;
+    case WG_H2: if constexpr (kHalf) go(conv_wgrad1d_h_kernel<T, 2>); break;
+    case WG_TR: if constexpr (kHalf) go(conv_wgrad1d_tr_kernel<T>); break;
+    case WG_TR_XBN: if constexpr (kHalf && !kF16) go(conv_wgrad1d_tr_kernel<T, true>); break;
+    default: break;
+  }
+  launch_wgrad_reduce(c.reduce, c.pl, st);
+  prof_end(ps, st);
+  return emsa_launch_status();
+}
+
+// the pointers of a job into its arguments (ws: NULL, or wgrad_ws_layout(pl).job_floats floats)
+void wgrad_bind(Wgrad1dPlan& pl, const void* in, const void* dout, float* dw, float* dbias, float* ws,
+                const float* in_scale, const float* in_shift) {
+  Wgrad1dArgs& w = pl.w;
   // (the argument structs carry byte addresses; the kernels read them through typed loaders)
-  const float* in = reinterpret_cast<const float*>(in_t);
-  const float* dout = reinterpret_cast<const float*>(dout_t);
+  w.in = (const float*)in; w.dout = (const float*)dout; w.dw = dw; w.dbias = dbias;
+  w.ws = ws;
+  w.ws_bias = ws ? ws + wgrad_ws_layout(pl).bias_off : nullptr;
+  w.in_scale = in_scale; w.in_shift = in_shift;
+}
+// algorithmic bytes: x and dy read once, the fp32 gradient written once
+double wgrad_algo_bytes(const EmsaConvGeom* g, size_t esize) {
+  return ((double)g->n_img * g->in_h * g->in_w * g->k_ch + (double)g->n_img * g->out_h * g->out_w * g->n_ch) * esize +
+         (double)g->kh * g->kw * g->n_ch * g->k_ch * 4.0;
+}
+
+template <typename T>
+int conv_wgrad_impl(const EmsaConvGeom* g, const void* in, const void* dout, float* dw, float* dbias,
+                    float* ws, const float* in_scale, const float* in_shift, void* stream) {
   if (!geom_ok(g) || geom_mapped(g)) return EMSA_E_SHAPE;
   if (!in || !dout || !dw) return EMSA_E_ARG;
-  if (kF16 && in_scale) return EMSA_E_ARG;          // the loader fold is a bf16 / fp32 form
   if (g->div_h != 1 || g->div_w != 1) return EMSA_E_SHAPE;
+  WgradChoice c = choose_wgrad(g, sizeof(T), std::is_same<T, emsa_f16>::value, in_scale != nullptr,
+                               ws != nullptr, in, dout);
+  if (c.kernel == WG_REFUSED) return c.err;        // decided before any profile region opens
   WgradArgs a;
   a.g = *g;
-  a.in = in; a.dout = dout; a.dw = dw; a.dbias = dbias;
+  a.in = (const float*)in; a.dout = (const float*)dout; a.dw = dw; a.dbias = dbias;
   a.M = g->n_img * g->out_h * g->out_w;
-  a.dout_aligned = dout_is_aligned(g, dout);
-  if (kHalf && (!a.dout_aligned || (((uintptr_t)in) & 7))) return EMSA_E_SHAPE;
+  a.dout_aligned = dout_is_aligned(g, a.dout);
   a.in_bytes = (uint32_t)((size_t)g->n_img * g->in_img_stride * sizeof(T));
   a.dout_bytes = (uint32_t)((size_t)a.M * g->ld_out * sizeof(T));
   a.div_ohw = make_fastdiv((uint32_t)(g->out_h * g->out_w));
   a.div_ow = make_fastdiv((uint32_t)g->out_w);
-  hipStream_t st = (hipStream_t)stream;
-  const int taps = g->kh * g->kw;
-  Wgrad1dPlan pl;
-  const bool direct16 = kHalf && direct16_geom(g);
-  if (direct16 && ((((uintptr_t)in) | ((uintptr_t)dout)) & 7)) return EMSA_E_SHAPE;
-  const bool one_d = plan_wgrad1d(g, a.dout_aligned != 0, pl, sizeof(T), direct16) &&
-                     (!kHalf || direct16 || (pl.wino && !kF16));
-  if (ws != nullptr && !one_d) return EMSA_E_SHAPE;   // ws_bytes(g) was 0
-  if (one_d) {
-    Wgrad1dArgs& w = pl.w;
-    w.in = in; w.dout = dout; w.dw = dw; w.dbias = dbias;
-    w.ws = ws;
-    w.in_scale = in_scale; w.in_shift = in_shift;
-    if (in_scale && !kHalf && (!pl.wino || w.R != 1)) return EMSA_E_SHAPE;
-    // (16-bit: the loader fold exists in the transposed-read kernel, conv_wgrad1d_tr_kernel<T, true>)
-    if (in_scale && kHalf && !(direct16 && pl.mode == 0 && w.R == 1)) return EMSA_E_SHAPE;
-    w.ws_bias = ws ? ws + (size_t)pl.ksplit * w.n_tiles * w.R * w.taps * 4096 : nullptr;
-    constexpr int BCO = 64, BCI = 64;
-    constexpr size_t lds = (size_t)(32 * BCO + 34 * BCI) * sizeof(float);
-    // algorithmic bytes: x and dy read once, the fp32 gradient written once
-    const double wbytes = (double)g->n_img * g->in_h * g->in_w * g->k_ch * sizeof(T) +
-                          (double)a.M * g->n_ch * sizeof(T) + (double)taps * g->n_ch * g->k_ch * 4.0;
-    const int ps = prof_begin(kHalf ? kProfClassWgradH : (w.R == 3 ? kProfClassWgrad3x3 : 7),
-                              algo_flops(a.g), st, wbytes);
-    static const bool bf16 = [] {
-      const char* e = getenv("EMSA_BF16_MFMA");
-      return e && e[0] == '1';
-    }();
-    if constexpr (kHalf) {
-      if (direct16) {
-        const dim3 grid(w.n_tiles * w.R * pl.ksplit);
-        if (in_scale && pl.mode != 0) {
-          prof_end(ps, st);
-          return EMSA_E_SHAPE;
-        }
-        if (pl.mode == 1)
-          hipLaunchKernelGGL((conv_wgrad1d_h_kernel<T, 1>), grid, dim3(256),
-                             (size_t)2 * 64 * kWH_ROW * sizeof(T), st, w);
-        else if (pl.mode == 2)
-          hipLaunchKernelGGL((conv_wgrad1d_h_kernel<T, 2>), grid, dim3(256),
-                             (size_t)3 * 64 * kWH_ROW * sizeof(T), st, w);
-        else if (wgrad16_tr() && !(g->k_ch & 7) && !(g->n_ch & 7) && !(g->ld_out & 7) &&
-                 !(g->in_px_stride & 7) && !(g->in_row_stride & 7) && !(g->in_img_stride & 7) &&
-                 !((((uintptr_t)in) | ((uintptr_t)dout)) & 15))
-        {
-          // (16-byte chunks: every pixel row of both tensors starts on a 16-byte boundary)
-          if (in_scale) {
-            // (no entry point hands fp16 a loader fold: that form is not instantiated)
-            if constexpr (!kF16)
-              hipLaunchKernelGGL((conv_wgrad1d_tr_kernel<T, true>), grid, dim3(256),
-                                 (size_t)2 * kWT_IMG * sizeof(T) + 2 * 64 * sizeof(float), st, w);
-          } else
-            hipLaunchKernelGGL((conv_wgrad1d_tr_kernel<T>), grid, dim3(256),
-                               (size_t)2 * kWT_IMG * sizeof(T), st, w);
-        } else if (in_scale) {
-          prof_end(ps, st);
-          return EMSA_E_SHAPE;                     // conv_wgrad1d_h_kernel has no loader fold
-        } else
-          hipLaunchKernelGGL((conv_wgrad1d_h_kernel<T, 0>), grid, dim3(256),
-                             (size_t)2 * 64 * kWH_ROW * sizeof(T), st, w);
-      } else if constexpr (!kF16)
-      // EMSA_WGRAD16=wino: E / D are formed in fp32 and rounded to bf16 as they enter LDS, one
-      // v_mfma_f32_32x32x16_bf16 per Winograd component and K step
-      hipLaunchKernelGGL((conv_wgrad1d_wino_kernel<BCO, BCI, true, T>),
-                         dim3(w.n_tiles * w.R * pl.ksplit), dim3(256),
-                         (size_t)(16 * 4 * (BCO + BCI)) * sizeof(float), st, w);
-    } else if (pl.wino && in_scale) {
-      // (tested BEFORE the opt-in bf16-MFMA form: that kernel has no loader fold and would
-      //  multiply against the raw BatchNorm input -- ADVICE r3; the fold stays exact fp32)
-      if constexpr (!kHalf)
-        hipLaunchKernelGGL((conv_wgrad1d_wino_kernel<BCO, BCI, false, float, true>),
-                           dim3(w.n_tiles * w.R * pl.ksplit), dim3(256),
-                           (size_t)(16 * 4 * (BCO + BCI) + 2 * BCI) * sizeof(float), st, w);
-    } else if (in_scale) {
-      prof_end(ps, st);
-      return EMSA_E_SHAPE;                         // direct form (EMSA_WGRAD_WINO=0): no loader fold
-    } else if (pl.wino && bf16)
-      hipLaunchKernelGGL((conv_wgrad1d_wino_kernel<BCO, BCI, true>),
-                         dim3(w.n_tiles * w.R * pl.ksplit), dim3(256),
-                         (size_t)(16 * 4 * (BCO + BCI)) * sizeof(float), st, w);
-    else if (pl.wino)
-      hipLaunchKernelGGL((conv_wgrad1d_wino_kernel<BCO, BCI>), dim3(w.n_tiles * w.R * pl.ksplit),
-                         dim3(256), (size_t)(16 * 4 * (BCO + BCI)) * sizeof(float), st, w);
-    else
-      hipLaunchKernelGGL((conv_wgrad1d_kernel<BCO, BCI>), dim3(w.n_tiles * w.R * pl.ksplit),
-                         dim3(256), lds, st, w);
-    static const bool rows_on = [] {
-      const char* e = getenv("EMSA_WGRAD_REDUCE_ROWS");
-      return !(e && e[0] == '0');
-    }();
-    if (ws != nullptr && rows_on && pl.ksplit <= 16 && w.n_tiles >= 32)
-      hipLaunchKernelGGL(wgrad1d_reduce_rows_kernel, dim3(w.n_tiles * 4 + w.n_co_tiles),
-                         dim3(256), 0, st, ws, w.ws_bias, pl.ksplit, w.n_tiles, w.n_ci_tiles,
-                         w.n_co_tiles, w.n_ch, w.k_ch, w.R, dw, dbias, w.taps);
-    else if (ws != nullptr)
-      hipLaunchKernelGGL(wgrad1d_reduce_kernel, dim3(w.n_tiles * w.R * w.taps * 64 + w.n_co_tiles),
-                         dim3(256), 0, st, ws, w.ws_bias, pl.ksplit, w.n_tiles, w.n_ci_tiles,
-                         w.n_co_tiles, w.n_ch, w.k_ch, w.R, dw, dbias, w.taps);
-    prof_end(ps, st);
-    return emsa_launch_status();
+  wgrad_bind(c.pl, in, dout, dw, dbias, ws, in_scale, in_shift);
+  return launch_wgrad_choice<T>(c, a, wgrad_algo_bytes(g, sizeof(T)), (hipStream_t)stream);
+}
+
+// THE storage type -> element type dispatch of the launching entry points (the workspace query needs
+// none: choose_wgrad is no template)
+int conv_wgrad_any(int32_t dtype, const EmsaConvGeom* g, const void* in, const void* dout, float* dw,
+                   float* dbias, float* ws, const float* in_scale, const float* in_shift, void* stream) {
+  if (dtype == EMSA_DT_F16 && in_scale) return EMSA_E_ARG;   // the loader fold is a bf16 / fp32 form
+  switch (dtype) {
+    case EMSA_DT_F32: return conv_wgrad_impl<float>(g, in, dout, dw, dbias, ws, in_scale, in_shift, stream);
+    case EMSA_DT_BF16: return conv_wgrad_impl<emsa_bf16>(g, in, dout, dw, dbias, ws, in_scale, in_shift, stream);
+    case EMSA_DT_F16: return conv_wgrad_impl<emsa_f16>(g, in, dout, dw, dbias, ws, in_scale, in_shift, stream);
+    default: return EMSA_E_ARG;
   }
-  if (in_scale) return EMSA_E_SHAPE;             // only the 1-D Winograd form folds the input's BN
-  if (taps == 7 && g->k_ch <= 32) return launch_wgrad<64, 32, 7, 2, 1, 2, T>(a, st);
-  if (taps == 2 && g->k_ch <= 32) return launch_wgrad<64, 32, 2, 2, 1, 2, T>(a, st);   // one-channel stem
-  if (taps == 1) {
-    // (a 128x128 tile was measured slower for the 1x1 convs: 96 / 82 us vs 66 / 63 us at 128 /
-    //  256 channels -- four times the split-K partial-tile volume per workgroup)
-    return launch_wgrad<64, 64, 1, 2, 2, 1, T>(a, st);
-  }
-  return launch_wgrad<64, 64, 3, 2, 2, 1, T>(a, st);
 }
 }  // namespace
 
+extern "C" int64_t emsa_conv_wgrad_ws_bytes(const EmsaConvGeom* g) {
+  return emsa_conv_wgrad_ws_bytes_t(EMSA_DT_F32, g);
+}
+// bytes of workspace for the deterministic two-pass weight gradient of `g` on activations of `dtype`
+// (the split-K plan depends on it; 0: not available for this geometry -> emsa_conv_wgrad_t
+// accumulates with atomics into the packed layout)
+extern "C" int64_t emsa_conv_wgrad_ws_bytes_t(int32_t dtype, const EmsaConvGeom* g) {
+  if (!geom_ok(g)) return 0;
+  const WgradChoice c = choose_wgrad(g, dtype == EMSA_DT_F32 ? sizeof(float) : 2, dtype == EMSA_DT_F16,
+                                     false, true, nullptr, nullptr);
+  return c.kernel == WG_REFUSED ? 0 : wgrad_ws_layout(c.pl).job_floats * (int64_t)sizeof(float);
+}
+
 extern "C" int emsa_conv_wgrad(const EmsaConvGeom* g, const float* in, const float* dout,
                                float* dw, float* dbias, float* ws, void* stream) {
-  return conv_wgrad_impl<float>(g, in, dout, dw, dbias, ws, stream);
+  return conv_wgrad_any(EMSA_DT_F32, g, in, dout, dw, dbias, ws, nullptr, nullptr, stream);
 }
 
 // Weight gradient of a conv whose input is a = relu(in * in_scale[c] + in_shift[c]) (the forward
@@ -2734,7 +2762,7 @@ extern "C" int emsa_conv_wgrad_inbn(const EmsaConvGeom* g, const float* in, cons
                                     float* dw, float* dbias, float* ws, const float* in_scale,
                                     const float* in_shift, void* stream) {
   if (!in_scale || !in_shift) return EMSA_E_ARG;
-  return conv_wgrad_impl<float>(g, in, dout, dw, dbias, ws, stream, in_scale, in_shift);
+  return conv_wgrad_any(EMSA_DT_F32, g, in, dout, dw, dbias, ws, in_scale, in_shift, stream);
 }
 
 // weight (+bias) gradient from activations in storage type `dtype` (training: EMSA_DT_BF16, or
@@ -2745,31 +2773,24 @@ extern "C" int emsa_conv_wgrad_inbn(const EmsaConvGeom* g, const float* in, cons
 extern "C" int emsa_conv_wgrad_t(int32_t dtype, const EmsaConvGeom* g, const void* in,
                                  const void* dout, float* dw, float* dbias, float* ws,
                                  void* stream) {
-  if (dtype == EMSA_DT_F32)
-    return conv_wgrad_impl<float>(g, (const float*)in, (const float*)dout, dw, dbias, ws, stream);
-  if (dtype == EMSA_DT_BF16)
-    return conv_wgrad_impl<emsa_bf16>(g, (const emsa_bf16*)in, (const emsa_bf16*)dout, dw, dbias,
-                                      ws, stream);
-  if (dtype == EMSA_DT_F16)
-    return conv_wgrad_impl<emsa_f16>(g, (const emsa_f16*)in, (const emsa_f16*)dout, dw, dbias,
-                                     ws, stream);
-  return EMSA_E_ARG;
+  return conv_wgrad_any(dtype, g, in, dout, dw, dbias, ws, nullptr, nullptr, stream);
 }
 
 // ---- several weight gradients in one launch (16-bit storage, conv_wgrad1d_tr_kernel) ----------
 namespace {
 // all jobs: stride-1 3-tap 1-D (or 3x3) convs the transposing-read kernel takes, same channel counts
 // and kernel rows; common split count from ONE budget of 768 workgroups
-bool plan_wgrad_multi(int n_jobs, const EmsaConvGeom* geoms, Wgrad1dPlan* pls, int& ksplit) {
-  if (n_jobs < 2 || n_jobs > kWgradMultiMax || !wgrad16_tr()) return false;
+// (in / dout / in_scale: arrays of n_jobs entries, or NULL for the workspace query: aligned, no fold)
+bool plan_wgrad_multi(int n_jobs, const EmsaConvGeom* geoms, const void* const* in,
+                      const void* const* dout, const float* const* in_scale, Wgrad1dPlan* pls) {
+  if (n_jobs < 2 || n_jobs > kWgradMultiMax) return false;
   for (int j = 0; j < n_jobs; ++j) {
     const EmsaConvGeom* g = geoms + j;
     if (!geom_ok(g) || geom_mapped(g) || g->div_h != 1 || g->div_w != 1) return false;
-    if (!direct16_geom(g) || !plan_wgrad1d(g, dout_is_aligned(g, nullptr), pls[j], 2, true)) return false;
-    if (pls[j].mode != 0) return false;
-    if ((g->k_ch & 7) || (g->n_ch & 7) || (g->ld_out & 7) || (g->in_px_stride & 7) ||
-        (g->in_row_stride & 7) || (g->in_img_stride & 7))
-      return false;
+    const WgradChoice c = choose_wgrad(g, 2, false, in_scale && in_scale[j], true, in ? in[j] : nullptr,
+                                       dout ? dout[j] : nullptr);
+    if (c.kernel != WG_TR && c.kernel != WG_TR_XBN) return false;
+    pls[j] = c.pl;
     if (pls[j].w.n_tiles != pls[0].w.n_tiles || pls[j].w.R != pls[0].w.R ||
         pls[j].w.n_ch != pls[0].w.n_ch || pls[j].w.k_ch != pls[0].w.k_ch)
       return false;
@@ -2801,12 +2822,9 @@ bool plan_wgrad_multi(int n_jobs, const EmsaConvGeom* geoms, Wgrad1dPlan* pls, i
     const int need = (w.steps_total + w.steps_per_split - 1) / w.steps_per_split;
     if (need > n_split) n_split = need;
   }
-  ksplit = n_split;           // (a job with fewer steps leaves its last split(s) empty: zero tiles)
+  // (a job with fewer steps leaves its last split(s) empty: zero tiles)
   for (int j = 0; j < n_jobs; ++j) pls[j].ksplit = n_split;
   return true;
-}
-int64_t wgrad_multi_job_floats(const Wgrad1dPlan& pl) {
-  return (int64_t)pl.ksplit * ((int64_t)pl.w.n_tiles * pl.w.R * pl.w.taps * 4096 + (int64_t)pl.w.n_co_tiles * 64);
 }
 }  // namespace
 
@@ -2815,10 +2833,9 @@ int64_t wgrad_multi_job_floats(const Wgrad1dPlan& pl) {
 extern "C" int64_t emsa_conv_wgrad_multi_ws_bytes(int32_t dtype, int32_t n_jobs, const EmsaConvGeom* geoms) {
   if (dtype != EMSA_DT_BF16 || !geoms) return 0;
   Wgrad1dPlan pls[kWgradMultiMax];
-  int ks = 0;
-  if (!plan_wgrad_multi(n_jobs, geoms, pls, ks)) return 0;
+  if (!plan_wgrad_multi(n_jobs, geoms, nullptr, nullptr, nullptr, pls)) return 0;
   int64_t fl = 0;
-  for (int j = 0; j < n_jobs; ++j) fl += wgrad_multi_job_floats(pls[j]);
+  for (int j = 0; j < n_jobs; ++j) fl += wgrad_ws_layout(pls[j]).job_floats;
   return fl * (int64_t)sizeof(float);
 }
 
@@ -2834,8 +2851,9 @@ int conv_wgrad_multi_impl(int32_t dtype, int32_t n_jobs, const EmsaConvGeom* geo
   if (dtype != EMSA_DT_BF16) return EMSA_E_ARG;
   if (!geoms || !in || !dout || !dw || !dbias || !ws) return EMSA_E_ARG;
   Wgrad1dPlan pls[kWgradMultiMax];
-  int ks = 0;
-  if (!plan_wgrad_multi(n_jobs, geoms, pls, ks)) return EMSA_E_SHAPE;
+  // (a misaligned pointer or a fold the transposed-read kernel does not take: no multi-job form)
+  if (!plan_wgrad_multi(n_jobs, geoms, in, dout, in_scale, pls)) return EMSA_E_SHAPE;
+  const int ks = pls[0].ksplit;
   hipStream_t st = (hipStream_t)stream;
   WgradMulti m;
   ReduceMulti r;
@@ -2845,24 +2863,14 @@ int conv_wgrad_multi_impl(int32_t dtype, int32_t n_jobs, const EmsaConvGeom* geo
   for (int j = 0; j < kWgradMultiMax; ++j) {
     const int k = j < n_jobs ? j : 0;             // (unused slots repeat job 0; never indexed)
     if (j < n_jobs) {
-      const EmsaConvGeom* g = geoms + j;
       if (!in[j] || !dout[j] || !dw[j]) return EMSA_E_ARG;
-      if ((((uintptr_t)in[j]) | ((uintptr_t)dout[j])) & 15) return EMSA_E_SHAPE;
-      Wgrad1dArgs& w = pls[j].w;
-      w.in = reinterpret_cast<const float*>(in[j]);
-      w.dout = reinterpret_cast<const float*>(dout[j]);
-      w.dw = dw[j];
-      w.dbias = dbias[j];
-      w.ws = wsp;
-      w.ws_bias = wsp + (size_t)ks * w.n_tiles * w.R * w.taps * 4096;
-      w.in_scale = in_scale ? in_scale[j] : nullptr;
-      w.in_shift = in_shift ? in_shift[j] : nullptr;
-      if ((w.in_scale == nullptr) != (w.in_shift == nullptr)) return EMSA_E_ARG;
-      any_xbn = any_xbn || w.in_scale != nullptr;
-      wsp += wgrad_multi_job_floats(pls[j]);
-      flops += algo_flops(*g);
-      bytes += (double)g->n_img * g->in_h * g->in_w * g->k_ch * 2.0 +
-               (double)g->n_img * g->out_h * g->out_w * g->n_ch * 2.0 + (double)g->kh * g->kw * g->n_ch * g->k_ch * 4.0;
+      wgrad_bind(pls[j], in[j], dout[j], dw[j], dbias[j], wsp, in_scale ? in_scale[j] : nullptr,
+                 in_shift ? in_shift[j] : nullptr);
+      if ((pls[j].w.in_scale == nullptr) != (pls[j].w.in_shift == nullptr)) return EMSA_E_ARG;
+      any_xbn = any_xbn || pls[j].w.in_scale != nullptr;
+      wsp += wgrad_ws_layout(pls[j]).job_floats;
+      flops += algo_flops(geoms[j]);
+      bytes += wgrad_algo_bytes(geoms + j, 2);
     }
     m.j[j] = pls[k].w;
     r.ws[j] = pls[k].w.ws; r.ws_bias[j] = pls[k].w.ws_bias; r.dw[j] = pls[k].w.dw; r.dbias[j] = pls[k].w.dbias;
@@ -2871,18 +2879,13 @@ int conv_wgrad_multi_impl(int32_t dtype, int32_t n_jobs, const EmsaConvGeom* geo
   r.splits = ks; r.n_tiles = w0.n_tiles; r.n_ci_tiles = w0.n_ci_tiles; r.n_co_tiles = w0.n_co_tiles;
   r.n_ch = w0.n_ch; r.k_ch = w0.k_ch; r.R = w0.R; r.taps = w0.taps;
   const int ps = prof_begin(kProfClassWgradH, flops, st, bytes);
-  if (any_xbn)
-    hipLaunchKernelGGL((conv_wgrad1d_tr_multi_kernel<emsa_bf16, true>), dim3(w0.n_tiles * w0.R * ks, n_jobs),
-                       dim3(256), (size_t)2 * kWT_IMG * sizeof(emsa_bf16) + 2 * 64 * sizeof(float), st, m);
-  else
-    hipLaunchKernelGGL((conv_wgrad1d_tr_multi_kernel<emsa_bf16>), dim3(w0.n_tiles * w0.R * ks, n_jobs),
-                       dim3(256), (size_t)2 * kWT_IMG * sizeof(emsa_bf16), st, m);
-  if (ks <= 16 && w0.n_tiles >= 32)
-    hipLaunchKernelGGL((wgrad1d_reduce_multi_kernel<true>), dim3(w0.n_tiles * 4 + w0.n_co_tiles, n_jobs),
-                       dim3(256), 0, st, r);
-  else
-    hipLaunchKernelGGL((wgrad1d_reduce_multi_kernel<false>),
-                       dim3(w0.n_tiles * w0.R * w0.taps * 64 + w0.n_co_tiles, n_jobs), dim3(256), 0, st, r);
+  hipLaunchKernelGGL((any_xbn ? conv_wgrad1d_tr_multi_kernel<emsa_bf16, true>
+                              : conv_wgrad1d_tr_multi_kernel<emsa_bf16>),
+                     dim3(w0.n_tiles * w0.R * ks, n_jobs), dim3(256),
+                     (size_t)2 * kWT_IMG * sizeof(emsa_bf16) + (any_xbn ? 2 * 64 * sizeof(float) : 0), st, m);
+  const WgradReduce kind = wgrad_reduce_kind(true, ks, w0.n_tiles);
+  hipLaunchKernelGGL(kind == WR_ROWS ? wgrad1d_reduce_multi_kernel<true> : wgrad1d_reduce_multi_kernel<false>,
+                     dim3(wgrad_reduce_grid(kind, w0), n_jobs), dim3(256), 0, st, r);
   prof_end(ps, st);
   return emsa_launch_status();
 }
@@ -2915,13 +2918,7 @@ extern "C" int emsa_conv_wgrad_inbn_t(int32_t dtype, const EmsaConvGeom* g, cons
                                       const void* dout, float* dw, float* dbias, float* ws,
                                       const float* in_scale, const float* in_shift, void* stream) {
   if (!in_scale || !in_shift) return EMSA_E_ARG;
-  if (dtype == EMSA_DT_F32)
-    return conv_wgrad_impl<float>(g, (const float*)in, (const float*)dout, dw, dbias, ws, stream,
-                                  in_scale, in_shift);
-  if (dtype == EMSA_DT_BF16)
-    return conv_wgrad_impl<emsa_bf16>(g, (const emsa_bf16*)in, (const emsa_bf16*)dout, dw, dbias,
-                                      ws, stream, in_scale, in_shift);
-  return EMSA_E_ARG;
+  return conv_wgrad_any(dtype, g, in, dout, dw, dbias, ws, in_scale, in_shift, stream);
 }
 
 // ---- profiling C-ABI -------------------------------------------------------------------------

@@ -1050,6 +1050,16 @@ def wgrad_wino2d_selected(spec):
     return (spec.cin, spec.cout) in WGRAD_WINO2D_SHAPES
 
 
+def _wgrad_outputs(spec, want_bias, dw_out, db_out, device, zero=False):
+    """flat (dw, db or None) a weight gradient is written to: `dw_out` / `db_out` when both are usable,
+    else one fresh buffer split into the two (zero=True: the atomics forms' accumulator, always fresh)"""
+    if not zero and dw_out is not None and (db_out is not None or not want_bias):
+        return dw_out.view(-1), db_out
+    nw = spec.kh * spec.kw * spec.cout * spec.cin
+    buf = (_zeros if zero else _empty)((nw + (spec.cout if want_bias else 0),), device)
+    return buf[:nw], (buf[nw:] if want_bias else None)
+
+
 def _conv_wgrad_wino2d(x, dy, spec, g, want_bias, like, dw_out, db_out):
     """-> (dw, db, packed) of conv_wgrad, or None: the library refuses this geometry"""
     global WGRAD_WINO2D_FALLBACKS
@@ -1058,16 +1068,10 @@ def _conv_wgrad_wino2d(x, dy, spec, g, want_bias, like, dw_out, db_out):
     if ws_bytes <= 0:
         WGRAD_WINO2D_FALLBACKS += 1
         return None
-    nw = 9 * spec.cout * spec.cin
     ws = _empty((ws_bytes // 4,), x.device)
-    if like is not None and dw_out is not None and (db_out is not None or not want_bias):
-        dw, db = dw_out.view(-1), db_out
-    else:
-        buf = _empty((nw + (spec.cout if want_bias else 0),), x.device)
-        dw = buf[:nw]
-        db = buf[nw:] if want_bias else None
-    # like = the weight: straight into the parameter layout; without it the packed form
+    # like = the weight: straight into the parameter layout; without it the packed form (never `dw_out`)
     packed = like is None
+    dw, db = _wgrad_outputs(spec, want_bias, None if packed else dw_out, db_out, x.device)
     check(L.emsa_conv_wgrad_wino2d(0, g, _p(x), _p(dy), _p(dw), _p(db), _p(ws), 1 if packed else 0,
                                    _stream()), 'emsa_conv_wgrad_wino2d')
     if packed:
@@ -1095,23 +1099,9 @@ def conv_wgrad(x, dy, spec, want_bias, like=None, two_pass=None, dw_out=None, db
         if res is not None:
             return res
     L = _lib.lib()
-    taps = spec.kh * spec.kw
-    nw = taps * spec.cout * spec.cin
-    nb = spec.cout if want_bias else 0
     ws_bytes = call_t('emsa_conv_wgrad_ws_bytes', dt(x), g) if (like is not None and two_pass) else 0
-    if ws_bytes > 0:
-        ws = _empty((ws_bytes // 4,), x.device)
-        if dw_out is not None and (db_out is not None or not want_bias):
-            dw, db = dw_out.view(-1), db_out
-        else:
-            buf = _empty((nw + nb,), x.device)
-            dw = buf[:nw]
-            db = buf[nw:] if want_bias else None
-    else:
-        buf = _zeros((nw + nb,), x.device)
-        ws = None
-        dw = buf[:nw]
-        db = buf[nw:] if want_bias else None
+    ws = _empty((ws_bytes // 4,), x.device) if ws_bytes > 0 else None
+    dw, db = _wgrad_outputs(spec, want_bias, dw_out, db_out, x.device, zero=ws is None)
     if x.dtype != dy.dtype:
         raise _lib.EmsaError(f"weight gradient of {x.dtype} activations with a {dy.dtype} gradient")
     if in_affine is not None and dt(x) != 0:
@@ -1176,13 +1166,7 @@ def conv_wgrad_multi(jobs):
         if aff and aff[0] is not None:
             a_sc[j], a_sh[j] = _p(aff[0][0]), _p(aff[0][1])
             any_aff = True
-        nw = spec.kh * spec.kw * spec.cout * spec.cin
-        if dw_out is not None and (db_out is not None or not want_bias):
-            dw, db = dw_out.view(-1), db_out
-        else:
-            buf = _empty((nw + (spec.cout if want_bias else 0),), dev)
-            dw = buf[:nw]
-            db = buf[nw:] if want_bias else None
+        dw, db = _wgrad_outputs(spec, want_bias, dw_out, db_out, dev)
         a_in[j], a_dy[j], a_dw[j], a_db[j] = _p(x), _p(dy), _p(dw), _p(db)
         outs.append((dw.view(like.shape), db))
     if any_aff:

@@ -620,15 +620,18 @@ class _Deferred:
 _WgradJob = collections.namedtuple('_WgradJob', 'x dy crt tw tb in_affine')
 
 
+def _bucket_view(dw, tw):
+    """the gradient-bucket view `tw` itself when the kernel wrote `dw` into it"""
+    return tw if tw is not None and dw.data_ptr() == tw.data_ptr() else dw
+
+
 def _wgrad_now(x, dy, crt, tw, tb, in_affine=None):
     conv = crt.conv
     dw, db, packed = Fn.conv_wgrad(x, dy, crt.spec, conv.bias is not None, like=conv.weight,
                                    dw_out=tw, db_out=tb, in_affine=in_affine)
     if packed:
-        dw = Fn.unpack_wgrad(dw, conv.weight, out=tw)
-    elif tw is not None and dw.data_ptr() == tw.data_ptr():
-        dw = tw
-    return dw, db
+        return Fn.unpack_wgrad(dw, conv.weight, out=tw), db
+    return _bucket_view(dw, tw), db
 
 
 def _launch_wgrads(jobs):
@@ -653,8 +656,7 @@ def _launch_wgrads(jobs):
                     res[i] = _wgrad_now(*jobs[i])
             else:
                 for i, (dw, db) in zip(part, out):
-                    tw = jobs[i].tw
-                    res[i] = (tw if tw is not None and dw.data_ptr() == tw.data_ptr() else dw, db)
+                    res[i] = (_bucket_view(dw, jobs[i].tw), db)
     return res
 
 
